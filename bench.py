@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: batched receding-horizon NMPC solves on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+`--dump-outputs DIR` writes, after the timed steps, what the headline leg's last timed step returned (u, cost, status,
+inner_it, outer_it, f2norm) as DIR/<name>.npy in float64, at most 64 MB in all (beyond that a fixed, seeded sample of rows,
+DIR/sample_rows.npy).  The scenes are seeded, so two builds run with the same arguments can be compared output for output.
 
 A step = one pass of the hot path over one batch: B independent cold-start solves (u0 = 0, what every
 reference call site does: src/interface_mpc.py:82 passes initial_guess=None) of the metric configuration
@@ -119,7 +123,12 @@ def parse_args(argv=None):
     ap.add_argument("--side-batch", type=int, default=32768, help="problems per GPU of the convergent / avoidance legs")
     ap.add_argument("--full", action="store_true", help="run the side legs on every rank of a multi-GPU run as well")
     ap.add_argument("--p-file", default=None, help=argparse.SUPPRESS)   # counter passes: the parent's parameter vectors (.npy)
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args) -> int:
@@ -193,6 +202,29 @@ def pmc_in_run(args, p_host):
         return None, f"{type(e).__name__}: {e}"
     finally:
         shutil.rmtree(raw, ignore_errors=True)
+
+
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: at most this much in all (every rank together)
+
+
+def dump_outputs(path, out, budget=DUMP_BUDGET_BYTES, prefix=""):
+    """--dump-outputs: the arrays the headline leg's last timed step handed back (the `out` dict of solve_device: u, cost,
+    status, inner_it, outer_it, f2norm), one `path/<prefix><name>.npy` each, as float64 (the int32 fields exactly).  When the
+    batch does not fit into `budget` bytes, the same fixed, seeded sample of rows is written for every array, and the row
+    numbers as `<prefix>sample_rows.npy`.  Returns the names written."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v) for k, v in out.items()}
+    b = len(next(iter(host.values())))
+    row_bytes = 8 * sum(int(np.prod(a.shape[1:], dtype=np.int64)) for a in host.values())
+    rows = None
+    if b * row_bytes > budget - 4096 * (len(host) + 1):           # 4 KiB per file for the .npy header, with room to spare
+        k = max(1, (budget - 4096 * (len(host) + 1)) // (row_bytes + 8))
+        rows = np.sort(np.random.default_rng(0).choice(b, size=k, replace=False))
+        host = {name: a[rows] for name, a in host.items()}
+        host["sample_rows"] = rows
+    for name, a in host.items():
+        np.save(os.path.join(path, f"{prefix}{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(host)
 
 
 class StubSolver:
@@ -398,6 +430,8 @@ def main():
     gen_s = time.perf_counter() - t_gen
     side = world == 1 or args.full   # side legs: one rank (or --full)
     leg = timed_leg(p, args.steps, args.warmup)
+    if args.dump_outputs:   # before any other leg reuses `out`; rank r > 0 of an N-rank run writes rank<r>_<name>.npy
+        dump_outputs(args.dump_outputs, out, DUMP_BUDGET_BYTES // world, prefix=f"rank{rank}_" if rank else "")
     # the control sequences of the first problems of the headline batch, for the parity figures next to the CPU baseline (below)
     head_u = None if stub else out["u"][:16384].cpu().numpy().copy()
     elapsed, per_rank_s = over_ranks(leg["elapsed"])

@@ -122,3 +122,39 @@ def test_cpu_baseline_reports_parity_of_the_run_on_its_sample():
     assert par["converged_on_both_sides"] == n_conv and par["same_converged_or_not"] == 1.0 and par["tolerance"] == 1e-3
     if conv[0] < S:
         assert abs(par["max_abs_du_on_them"] - 1e-6) < 1e-12
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the arrays of the headline leg's last timed step, one float64 .npy each, with --steps timed steps."""
+    import numpy as np
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64",
+                        "--cpu-seconds", "0", "--dump-outputs", str(d)],
+                       env=_env(MPCGPU_BENCH_STUB="1"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    names = sorted(f.name for f in d.iterdir())
+    assert names == sorted(f"{k}.npy" for k in ("u", "cost", "status", "inner_it", "outer_it", "f2norm")), names
+    u = np.load(d / "u.npy")
+    assert u.dtype == np.float64 and u.shape == (64, 40) and not u.any()          # what the stub solver wrote
+    assert np.array_equal(np.load(d / "inner_it.npy"), np.full(64, 7.0))
+    assert np.array_equal(np.load(d / "status.npy"), np.ones(64))
+
+
+def test_dump_outputs_samples_the_same_rows_when_over_budget(tmp_path):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    B = 1000
+    out = {"u": np.arange(B * 40, dtype=np.float64).reshape(B, 40), "status": np.arange(B, dtype=np.int32)}
+    budget = 100 * 8 * 41 + 4096 * 3 + 100 * 8
+    names = bench.dump_outputs(str(tmp_path), out, budget=budget)
+    assert names == ["sample_rows", "status", "u"]
+    rows = np.load(tmp_path / "sample_rows.npy")
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "status.npy"), rows)
+    assert np.array_equal(np.load(tmp_path / "u.npy")[:, 0], rows * 40)
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= budget
+    bench.dump_outputs(str(tmp_path / "again"), out, budget=budget)
+    assert np.array_equal(np.load(tmp_path / "again" / "sample_rows.npy"), rows)     # fixed seed: the same sample every run
