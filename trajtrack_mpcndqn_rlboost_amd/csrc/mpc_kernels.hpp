@@ -1008,6 +1008,27 @@ __device__ __forceinline__ DynItem dyn_item(const Ctx& cx, int i, int k, int N, 
     return d;
 }
 
+// Squared distance from (px, py) to the reference segment of record sg (s1, s2 - s1, 1 / (|s2 - s1|^2 + 1e-16); mpc_generator.py:
+// 28-36) and its gradient with respect to the position, with CasADi's sub-gradient of the clamp fmin(fmax(t, 0), 1): the
+// derivative of t passes on [0, 1] inclusive.  ONE definition for every site of eval_point: the tie walk recomputes the
+// distance of a segment and must get the bits the item lane got for it.
+struct SegDist {
+    double dx, dy, inv, th, wx, wy, d2;
+    __device__ __forceinline__ SegDist(const double* sg, double px, double py) {
+        const double s1x = sg[0], s1y = sg[1];
+        dx = sg[2]; dy = sg[3]; inv = sg[4];
+        th = ((px - s1x) * dx + (py - s1y) * dy) * inv;
+        const double t = clampd(th, 0.0, 1.0);
+        wx = s1x + t * dx - px; wy = s1y + t * dy - py;
+        d2 = wx * wx + wy * wy;
+    }
+    __device__ __forceinline__ void grad(double& gx, double& gy) const {
+        const double wd = (th >= 0.0 && th <= 1.0) ? (wx * dx + wy * dy) * inv : 0.0;
+        gx = 2.0 * (wd * dx - wx);
+        gy = 2.0 * (wd * dy - wy);
+    }
+};
+
 // ------------------------------------------------------------------------------------------------
 // psi(u; c, y), f(u), F1, F2 and (optionally) grad psi at the point held by the vector lanes.
 // ------------------------------------------------------------------------------------------------
@@ -1170,16 +1191,10 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
         MPC_ITEM_LOOP
         for (int it = 0; it < SEG_WIN && i < N; ++it, i += LPS) {
             const double* sg = cx.seg + SEGW * i;
-            const double s1x = sg[0], s1y = sg[1], dx = sg[2], dy = sg[3], inv = sg[4];
-            const double th = ((px - s1x) * dx + (py - s1y) * dy) * inv;
-            const double t = clampd(th, 0.0, 1.0);
-            const double wx = s1x + t * dx - px, wy = s1y + t * dy - py;
-            const double d2 = wx * wx + wy * wy;
-            if (d2 < best) {
-                best = d2;
-                const double wd = (th >= 0.0 && th <= 1.0) ? (wx * dx + wy * dy) * inv : 0.0;
-                bgx = 2.0 * (wd * dx - wx);
-                bgy = 2.0 * (wd * dy - wy);
+            const SegDist sd(sg, px, py);
+            if (sd.d2 < best) {
+                best = sd.d2;
+                sd.grad(bgx, bgy);
             }
         }
         // (2) every later segment of this lane lies in the bounding circle stored with segment i (the circle of ALL segments
@@ -1198,17 +1213,11 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
             MPC_ITEM_LOOP
             while (more) {
                 const double* sg = cx.seg + SEGW * i;
-                const double s1x = sg[0], s1y = sg[1], dx = sg[2], dy = sg[3], inv = sg[4];
-                const double th = ((px - s1x) * dx + (py - s1y) * dy) * inv;
-                const double t = clampd(th, 0.0, 1.0);
-                const double wx = s1x + t * dx - px, wy = s1y + t * dy - py;
-                const double d2 = wx * wx + wy * wy;
-                if (d2 < best) {
-                    best = d2;
-                    sb = sqrt_upper(d2, KC(K_SQRT));
-                    const double wd = (th >= 0.0 && th <= 1.0) ? (wx * dx + wy * dy) * inv : 0.0;
-                    bgx = 2.0 * (wd * dx - wx);
-                    bgy = 2.0 * (wd * dy - wy);
+                const SegDist sd(sg, px, py);
+                if (sd.d2 < best) {
+                    best = sd.d2;
+                    sb = sqrt_upper(sd.d2, KC(K_SQRT));
+                    sd.grad(bgx, bgy);
                 }
                 i += LPS;
                 more = false;
@@ -1543,12 +1552,32 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
     double Gx = Gpx, Gy = Gpy, vcost = 0.0;
     if (c_vl) {
         double bb = inf, wbx = 0.0, wby = 0.0;
+        bool tie = false;
         Gx += gx; Gy += gy;
         if (best < bb) { bb = best; wbx = bgx; wby = bgy; }
         for (int s = 1; s < LPS; ++s) {
             const double* pp = cx.part + ((s - 1) * N + lane) * PARTW;
             Gx += pp[0]; Gy += pp[1];
             if (pp[2] < bb) { bb = pp[2]; wbx = pp[3]; wby = pp[4]; }
+            else if (pp[2] == bb) tie = true;
+        }
+        // An EXACT tie between item lanes.  The reference folds fmin over the segments in index order (mmin,
+        // mpc_generator.py:127): the EARLIEST segment at the minimum wins, and with it its nearest point -- the gradient.  Lane
+        // sub holds segments k + sub, k + sub + LPS, ...: the earliest of two tying segments may sit in any lane, so the lane
+        // order above does not decide.  Rare (a tie needs exactly representable geometry, e.g. u = 0 on a dyadic path): the
+        // vector lane walks the segments of its step in index order to the first one at distance bb.  SegDist is the item
+        // lanes' own evaluation, so the distance and the gradient are the bits an item lane computed for that segment.
+        // (`tie` is also set by two lanes that tie ABOVE the final minimum: the walk then finds the one segment at bb and
+        // returns what the lane order chose -- harmless, and as rare.)
+        if (tie) {
+            const double qx = cx.pos[2 * lane], qy = cx.pos[2 * lane + 1];   // = px, py of this lane (re-read: nothing keeps
+            for (int i = lane; i < N; ++i) {                                  // them live through phase B for a rare path)
+                const SegDist sd(cx.seg + SEGW * i, qx, qy);
+                if (sd.d2 == bb) {
+                    sd.grad(wbx, wby);
+                    break;
+                }
+            }
         }
         if (BAL && want_grad && lane >= NL2) { Gx += cx.bal[2 * (lane - NL2)]; Gy += cx.bal[2 * (lane - NL2) + 1]; }   // foreign items of this step
         Gx += HD(H_QRPD) * wbx; Gy += HD(H_QRPD) * wby;
