@@ -93,6 +93,53 @@ int32_t mpcgpu_env_step_autoreset_dev(int32_t device, const mpcgpu_env_params* p
                                       double* reward, uint8_t* terminated, uint8_t* truncated, float* terminal_obs_internal,
                                       float* terminal_obs_external, int32_t max_episode_steps, void* stream);
 
+/*
+ * Image-observation variant: TrajectoryPlannerEnvironmentImgsReward1 (variants/imgs_reward1.py:7-49).  The internal
+ * observation, reward, flags and state are exactly those of the entries above; the external observation is
+ * components/ext_obsv_image.py: uint8 [B x 3 x H x W], channel-first --
+ *   channel 0: padded boundary filled with 255, then every padded obstacle outline at the current clock filled with 0;
+ *   channel 1: the same with the obstacles at the OLDEST of the last 6 observations since the reset (ext_obsv_image.py:52-71);
+ *   channel 2: the constant distance field (ext_obsv_image.py:42-50), computed by the caller once and passed as [H x W].
+ * Both images are rasterised at 2W x 2H (cv2.fillPoly, LINE_8, shift 0, as restated in DESIGN.md) and halved
+ * (cv2.resize INTER_LINEAR at exactly half size = the rounded mean of each 2 x 2 block).  Every observation -- steps,
+ * observe-only calls, the observation after an in-kernel reset -- pushes the obstacle history; an in-kernel reset clears
+ * it first (environment.py:161-180).
+ */
+typedef struct mpcgpu_env_img_params {
+    int32_t width, height;   /* W, H of the final image: 8..96 each (54 x 54 in the reference) */
+    int32_t down_sample;     /* 2 -- the only value built */
+    int32_t reserved;
+    double scale_x, scale_y; /* 1 / (width of the depicted area), 1/18 */
+    double center_x, center_y; /* where the robot sits in the image, 0.5, 0.3 */
+    double angle;            /* rotation of the image, 0 */
+} mpcgpu_env_img_params;
+
+/* doubles of per-environment image state (observation count and obstacle-clock history; zero = freshly reset),
+ * < 0 on invalid image params (no device needed) */
+int32_t mpcgpu_env_img_state_doubles(const mpcgpu_env_img_params* img);
+
+/*
+ * mpcgpu_env_step_dev with the image observation: img_state [B x mpcgpu_env_img_state_doubles], distance_field [H x W]
+ * uint8, obs_image [B x 3 x H x W] uint8.  Two kernels on `stream`: the environment step, then the rasteriser.
+ */
+int32_t mpcgpu_env_step_imgs_dev(int32_t device, const mpcgpu_env_params* params, const mpcgpu_env_img_params* img,
+                                 int32_t B, const double* records, double* state, double* img_state,
+                                 const uint8_t* distance_field, const int32_t* action, float* obs_internal,
+                                 uint8_t* obs_image, double* reward, uint8_t* terminated, void* stream);
+
+/*
+ * mpcgpu_env_step_autoreset_dev with the image observation.  For an environment whose episode ended, terminal_obs_image
+ * receives the image it ended in (drawn from the pose and clock before the reset, with the history up to that step) and
+ * obs_image the first image of the next episode (history cleared).  terminal_obs_internal / terminal_obs_image may be NULL.
+ */
+int32_t mpcgpu_env_step_imgs_autoreset_dev(int32_t device, const mpcgpu_env_params* params,
+                                           const mpcgpu_env_img_params* img, int32_t B, const double* records,
+                                           double* state, double* img_state, const uint8_t* distance_field,
+                                           const int32_t* action, float* obs_internal, uint8_t* obs_image,
+                                           double* reward, uint8_t* terminated, uint8_t* truncated,
+                                           float* terminal_obs_internal, uint8_t* terminal_obs_image,
+                                           int32_t max_episode_steps, void* stream);
+
 const char* mpcgpu_env_last_error(void);
 
 #ifdef __cplusplus

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Secondary benchmark: environment steps per second of the fused HIP step kernel.
 
-    python tools/bench_env.py [--batch B] [--steps K] [--warmup W] [--cpu-seconds S]
+    python tools/bench_env.py [--variant rays|imgs] [--batch B] [--steps K] [--warmup W] [--cpu-seconds S]
 
 Prints ONE JSON line in the shape of bench.py's (metric / value / roofline / cpu_baseline).  A step = one
 ``env.step`` of B environments (two maps of tests/golden/env_rays_traces.npz, alternating), random actions, records
 and state resident in HBM.  Algorithmic bytes per environment step: the map record (read once) + 2 x 256 B of state +
-action + the two observation vectors + reward + flag.  The CPU leg is the numpy oracle (one core, bounded sample)."""
+action + the two observation vectors + reward + flag.  The CPU leg is the numpy oracle (one core, bounded sample).
+``--variant imgs``: the image-observation environment (rl_env.BatchedImgsEnv, two kernels per step); its algorithmic bytes
+replace the ray vector by the 3 W H image write and add the image state (2 x 128 B); its CPU leg is the numpy
+restatement of tests/support/image_obs_numpy.py."""
 import argparse
 import importlib
 import json
@@ -40,13 +43,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--variant", choices=("rays", "imgs"), default="rays")
     args = ap.parse_args()
     fx = np.load(os.path.join(ROOT, "tests", "golden", "env_rays_traces.npz"))
     specs = json.loads(bytes(fx["specs_json"]).decode())
     maps = [rl_env.make_map(sp["boundary"], sp["static"], sp["dynamic"], sp["start"], sp["goal"], sp["path"])
             for sp in specs.values()]
     B = args.batch
-    env = rl_env.BatchedRaysEnv([maps[i % len(maps)] for i in range(B)])
+    imgs = args.variant == "imgs"
+    env = (rl_env.BatchedImgsEnv if imgs else rl_env.BatchedRaysEnv)([maps[i % len(maps)] for i in range(B)])
     env.reset()
     acts = torch.randint(0, 9, (args.warmup + args.steps, B), device=env.device, dtype=torch.int32)
     for t in range(args.warmup):
@@ -63,6 +68,8 @@ def main():
     k_ms = e0.elapsed_time(e1) / args.steps
     rec_bytes = env.records.shape[1] * 8
     algo = rec_bytes + 2 * 8 * rl_env.STATE_DOUBLES + 4 + 4 * (rl_env.N_INTERNAL + rl_env.N_EXTERNAL) + 8 + 1
+    if imgs:
+        algo += -4 * rl_env.N_EXTERNAL + env.obs_image[0].numel() + 2 * 8 * env.img_state.shape[1]
     achieved = algo * B / (k_ms * 1e-3) / 1e9
     line = {"metric": "DRL environment steps/sec (batch, rays + R1 reward)", "value": B * args.steps / elapsed,
             "unit": "env-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -72,9 +79,17 @@ def main():
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic(B), "kernel": "env_step_kernel",
                          "kernel_ms": k_ms, "algorithmic_bytes_per_env_step": algo}}
+    if imgs:
+        line["metric"] = "DRL environment steps/sec (batch, 54 x 54 images + R1 reward)"
+        line["roofline"].update(kernel="env_step_kernel + env_img_kernel", traffic=None)
     if args.cpu_seconds > 0:
         from oracle import rl_env_numpy as orc
-        o = orc.OracleRaysEnv(maps[0])
+        if imgs:
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            from support.image_obs_numpy import OracleImgsEnv
+            o = OracleImgsEnv(maps[0])
+        else:
+            o = orc.OracleRaysEnv(maps[0])
         rng = np.random.default_rng(0)
         n, t0 = 0, time.perf_counter()
         while time.perf_counter() - t0 < args.cpu_seconds:

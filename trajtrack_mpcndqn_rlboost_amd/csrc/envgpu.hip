@@ -12,7 +12,7 @@
 #include <cstdio>
 #include <string>
 
-#include "../../include/mpcgpu_env.h"
+#include "envgpu_internal.hpp"
 
 namespace envgpu {
 
@@ -24,14 +24,9 @@ constexpr int SDIM = MPCGPU_ENV_STATE_DOUBLES;
 constexpr int MAX_OBST = 31;
 constexpr double L_SECTOR = 1000.0;  // ext_obsv_sector_and_ray.py:32
 
-struct EnvK {
-    mpcgpu_env_params p;
-    int rec, o_cum, o_len, o_xy, o_anim, an, o_edge;
-};
-
 __host__ __device__ inline int anim_doubles(int K) { return 4 + (K + 1) + 3 * K; }
 
-static bool layout(const mpcgpu_env_params& p, EnvK& k) {
+bool layout(const mpcgpu_env_params& p, EnvK& k) {
     if (p.n_path_max < 2 || p.n_path_max > WAVE || p.n_obst_max < 0 || p.n_obst_max > MAX_OBST || p.n_kf_max < 1 ||
         p.n_kf_max > 4 || p.n_edge_max < 1)
         return false;
@@ -104,12 +99,6 @@ __constant__ double DIRS[16] = {0.0, 0.38268343236508978178, 0.70710678118654757
                                 1.0, 0.92387953251128673848, 0.70710678118654757274, 0.38268343236508978178,
                                 0.0, -0.38268343236508978178, -0.70710678118654757274, -0.92387953251128673848,
                                 -1.0, -0.92387953251128673848, -0.70710678118654757274, -0.38268343236508978178};
-
-struct EnvOut {
-    float* obs_int; float* obs_ext; double* reward; uint8_t* terminated;
-    // in-kernel auto-reset (max_steps > 0): time-limit flag, and where the observation an episode ENDED in is kept
-    uint8_t* truncated; float* term_int; float* term_ext; int max_steps;
-};
 
 __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double* __restrict__ rec_all, double* state_all,
                                                         const int32_t* __restrict__ action, EnvOut out, int B) {
@@ -314,9 +303,11 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
         // inside a padded obstacle the robot itself belongs to sector ∩ obstacle: every distance is 0
         const double d = in_obstacle ? 0.0 : (idx < NSEG ? sqrt(red) : red);
         const float o = (float)normalize_distance(d);
-        float* oe = obs_ext + (size_t)b * MPCGPU_ENV_EXTERNAL_OBS;
-        oe[idx] = o;
-        oe[2 * NSEG + idx] = (float)st[8 + idx];
+        if (obs_ext) {   // NULL for the image variant, which keeps only the memory in the state
+            float* oe = obs_ext + (size_t)b * MPCGPU_ENV_EXTERNAL_OBS;
+            oe[idx] = o;
+            oe[2 * NSEG + idx] = (float)st[8 + idx];
+        }
         st[8 + idx] = (double)o;
     }
 
@@ -404,6 +395,11 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
             if (terminated) terminated[b] = (collided || reached) ? 1 : 0;
             if (out.truncated) out.truncated[b] = timeout ? 1 : 0;
             st[26] = (double)flags;   // flags of this step, still readable after an in-kernel reset
+            if (out.pre_reset) {      // image variant: what the terminal image is drawn from
+                double* pr = out.pre_reset + (size_t)b * IMG_STATE + IMG_PRE;
+                pr[0] = x; pr[1] = y; pr[2] = th; pr[3] = clock;
+                pr[4] = (out.max_steps > 0 && act && (collided || reached || timeout)) ? 1.0 : 0.0;
+            }
         }
         st[0] = x; st[1] = y; st[2] = th; st[3] = v; st[4] = w; st[5] = clock;
         st[6] = (act || pass == 1) ? (pass == 1 ? 0.0 : progress) : last_prog;
@@ -432,12 +428,28 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
 }
 
 thread_local std::string g_err;
-static int fail(const char* what, hipError_t e = hipSuccess) {
+int fail(const char* what, hipError_t e) {
     char buf[256];
     if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
     else snprintf(buf, sizeof buf, "%s", what);
     g_err = buf;
     return -1;
+}
+
+int launch_step(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records, double* state,
+                const int32_t* action, EnvOut out, bool need_ext, void* stream) {
+    EnvK k;
+    if (!params || !layout(*params, k)) return fail("invalid mpcgpu_env_params (P 2..64, M 0..31, K 1..4, E >= 1)");
+    if (params->num_segments != NSEG || params->corner_samples != NCORNER)
+        return fail("only num_segments = 8 and corner_samples = 3 are built (rays_reward1.py:18-20)");
+    if (B < 0 || !records || !state || !out.obs_int || (need_ext && !out.obs_ext)) return fail("null pointer / negative batch");
+    if (B == 0) return 0;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail("hipSetDevice", e);
+    hipLaunchKernelGGL(env_step_kernel, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state, action, out, (int)B);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail("env_step_kernel launch", e);
+    return 0;
 }
 
 }  // namespace envgpu
@@ -450,28 +462,11 @@ int32_t mpcgpu_env_record_doubles(const mpcgpu_env_params* params) {
     return k.rec;
 }
 
-static int32_t launch_env(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records, double* state,
-                          const int32_t* action, envgpu::EnvOut out, void* stream) {
-    using namespace envgpu;
-    EnvK k;
-    if (!params || !layout(*params, k)) return fail("invalid mpcgpu_env_params (P 2..64, M 0..31, K 1..4, E >= 1)");
-    if (params->num_segments != NSEG || params->corner_samples != NCORNER)
-        return fail("only num_segments = 8 and corner_samples = 3 are built (rays_reward1.py:18-20)");
-    if (B < 0 || !records || !state || !out.obs_int || !out.obs_ext) return fail("null pointer / negative batch");
-    if (B == 0) return 0;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail("hipSetDevice", e);
-    hipLaunchKernelGGL(env_step_kernel, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state, action, out, (int)B);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail("env_step_kernel launch", e);
-    return 0;
-}
-
 int32_t mpcgpu_env_step_dev(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records,
                             double* state, const int32_t* action, float* obs_internal, float* obs_external,
                             double* reward, uint8_t* terminated, void* stream) {
-    envgpu::EnvOut out{obs_internal, obs_external, reward, terminated, nullptr, nullptr, nullptr, 0};
-    return launch_env(device, params, B, records, state, action, out, stream);
+    envgpu::EnvOut out{obs_internal, obs_external, reward, terminated, nullptr, nullptr, nullptr, 0, nullptr};
+    return envgpu::launch_step(device, params, B, records, state, action, out, true, stream);
 }
 
 int32_t mpcgpu_env_step_autoreset_dev(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records,
@@ -481,8 +476,8 @@ int32_t mpcgpu_env_step_autoreset_dev(int32_t device, const mpcgpu_env_params* p
     if (!action) return envgpu::fail("auto-reset needs actions (use mpcgpu_env_step_dev to observe)");
     if (max_episode_steps <= 0) return envgpu::fail("max_episode_steps must be positive");
     envgpu::EnvOut out{obs_internal, obs_external, reward, terminated, truncated, terminal_obs_internal,
-                       terminal_obs_external, max_episode_steps};
-    return launch_env(device, params, B, records, state, action, out, stream);
+                       terminal_obs_external, max_episode_steps, nullptr};
+    return envgpu::launch_step(device, params, B, records, state, action, out, true, stream);
 }
 
 const char* mpcgpu_env_last_error(void) { return envgpu::g_err.c_str(); }

@@ -1,0 +1,40 @@
+// envgpu_internal.hpp -- what the image-observation entries (envimg.hip) share with the environment step (envgpu.hip).
+// Not part of the C-ABI: the public declarations are in include/mpcgpu_env.h.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/mpcgpu_env.h"
+
+namespace envgpu {
+
+struct EnvK {
+    mpcgpu_env_params p;
+    int rec, o_cum, o_len, o_xy, o_anim, an, o_edge;
+};
+
+struct EnvOut {
+    float* obs_int; float* obs_ext; double* reward; uint8_t* terminated;
+    // in-kernel auto-reset (max_steps > 0): time-limit flag, and where the observation an episode ENDED in is kept
+    uint8_t* truncated; float* term_int; float* term_ext; int max_steps;
+    // image variant only (NULL otherwise): per-environment image state (IMG_STATE doubles) that receives, at IMG_PRE..+4,
+    // the pose and clock the step observed BEFORE an in-kernel reset and whether that reset happened
+    double* pre_reset;
+};
+
+// per-environment image state (mpcgpu_env_img_state_doubles): [0] observations since the last reset, [1..6] obstacle
+// clock of each of the last 6 observations (ring, slot (k - 1) % 6 holds observation k), [7] reserved,
+// [8..11] x, y, theta, clock of the last step before an in-kernel reset, [12] 1 when that reset happened, [13..15] reserved
+constexpr int IMG_STATE = 16;
+constexpr int IMG_HIST = 6;
+constexpr int IMG_PRE = 8;
+
+bool layout(const mpcgpu_env_params& p, EnvK& k);
+int fail(const char* what, hipError_t e = hipSuccess);
+// validates params and pointers (obs_ext may be NULL when need_ext is false) and enqueues env_step_kernel
+int launch_step(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records, double* state,
+                const int32_t* action, EnvOut out, bool need_ext, void* stream);
+
+}  // namespace envgpu

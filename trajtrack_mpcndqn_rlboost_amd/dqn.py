@@ -3,6 +3,10 @@
 * ``QNetwork``: the ray-observation model of the reference -- SB3 ``DQN('MultiInputPolicy')`` with
   ``net_arch=[16, 16]``: 46 -> 16 -> 16 -> 9, ReLU (``src/test_block_rl.py:40-53,77-86``; input = ``external``(32)
   then ``internal``(14), dict keys sorted).  Plain ``torch.nn`` on PyTorch-ROCm: 1 177 parameters, no custom kernel.
+* ``ImageQNetwork``: the image-observation model -- SB3 ``DQN('MultiInputPolicy')`` with ``net_arch=[64, 64]`` on
+  ``TrajectoryPlannerEnvironmentImgsReward1`` (``src/test_block_rl.py:40-46,77-86``): CombinedExtractor = NatureCNN on
+  ``external / 255`` (uint8 [3, H, W] -> 256) then Flatten on ``internal`` (14), head 270 -> 64 -> 64 -> 9.  SB3's
+  parameter names, so an SB3 archive's ``policy.pth`` loads as it is.
 * ``rl_reference``: what ``src/main.py:193-202`` does with the chosen action -- copy the agent, apply the action for
   one step (``src/pkg_dqn/environment/agent.py:102-145``), then 19 steps at reference speed 1.0 with the angular
   velocity decaying by 0.95 per step (``agent.py:86-100``) -- vectorised over the batch.
@@ -60,6 +64,67 @@ class QNetwork(nn.Module):
             sd = torch.load(io.BytesIO(z.read("policy.pth")), weights_only=True)
         return cls().load_arrays({f"w{i}_{k}": sd[f"q_net.q_net.{i}.{k}"].numpy() for i in (0, 2, 4)
                                   for k in ("weight", "bias")})
+
+
+class NatureCNN(nn.Module):
+    """SB3 ``NatureCNN`` (Mnih et al. 2015): three convolutions and one linear layer, ReLU after each."""
+
+    def __init__(self, in_channels: int = 3, height: int = 54, width: int = 54, features_dim: int = 256):
+        super().__init__()
+        self.cnn = nn.Sequential(nn.Conv2d(in_channels, 32, kernel_size=8, stride=4, padding=0), nn.ReLU(),
+                                 nn.Conv2d(32, 64, kernel_size=4, stride=2, padding=0), nn.ReLU(),
+                                 nn.Conv2d(64, 64, kernel_size=3, stride=1, padding=0), nn.ReLU(), nn.Flatten())
+        with torch.no_grad():
+            n_flatten = self.cnn(torch.zeros(1, in_channels, height, width)).shape[1]
+        self.linear = nn.Sequential(nn.Linear(n_flatten, features_dim), nn.ReLU())
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.linear(self.cnn(x))
+
+
+class _CombinedExtractor(nn.Module):
+    """SB3 ``CombinedExtractor`` for {'external': image, 'internal': vector}: sorted keys, images scaled by 1/255
+    (``preprocess_obs`` for a uint8 image space), vectors flattened."""
+
+    def __init__(self, image_shape, features_dim: int = 256):
+        super().__init__()
+        self.extractors = nn.ModuleDict({"external": NatureCNN(*image_shape, features_dim=features_dim),
+                                         "internal": nn.Flatten()})
+
+    def forward(self, obs: Dict[str, torch.Tensor]) -> torch.Tensor:
+        return torch.cat([self.extractors["external"](obs["external"].float() / 255.0),
+                          self.extractors["internal"](obs["internal"].float())], dim=1)
+
+
+class ImageQNetwork(nn.Module):
+    """The image agent's Q-network; ``forward`` takes the observation dictionary of ``rl_env.BatchedImgsEnv``."""
+
+    def __init__(self, image_shape=(3, 54, 54), n_internal: int = 14, hidden=(64, 64), n_actions: int = N_ACTIONS,
+                 features_dim: int = 256):
+        super().__init__()
+        self.features_extractor = _CombinedExtractor(tuple(image_shape), features_dim)
+        layers, d = [], features_dim + n_internal
+        for h in hidden:
+            layers += [nn.Linear(d, h), nn.ReLU()]
+            d = h
+        layers.append(nn.Linear(d, n_actions))
+        self.q_net = nn.Sequential(*layers)
+
+    def forward(self, obs: Dict[str, torch.Tensor]) -> torch.Tensor:
+        return self.q_net(self.features_extractor(obs))
+
+    @torch.no_grad()
+    def greedy_actions(self, obs: Dict[str, torch.Tensor]) -> torch.Tensor:
+        return self.forward(obs).argmax(dim=1)
+
+    @classmethod
+    def from_sb3_zip(cls, path: str, image_shape=(3, 54, 54)) -> "ImageQNetwork":
+        """Read the ``q_net.*`` entries of ``policy.pth`` in an SB3 ``model.save`` archive of the image agent."""
+        with zipfile.ZipFile(path) as z:
+            sd = torch.load(io.BytesIO(z.read("policy.pth")), weights_only=True)
+        net = cls(image_shape)
+        net.load_state_dict({k[len("q_net."):]: v for k, v in sd.items() if k.startswith("q_net.")})
+        return net
 
 
 def observation_vector(obs: Dict[str, np.ndarray]) -> np.ndarray:

@@ -17,7 +17,7 @@ import torch.distributed as dist
 from torch import nn
 from torch.nn import functional as F
 
-from .dqn import QNetwork
+from .dqn import ImageQNetwork, QNetwork
 
 
 class DqnTrainer:
@@ -258,6 +258,58 @@ class ReplayBuffer:
                     next_obs=self.next_obs[idx], dones=self.dones[idx])
 
 
+class ImageReplayBuffer:
+    """The same ring buffer for the image observation: images stay uint8 (3 H W bytes each, 8 748 at 54 x 54), the
+    internal observation float32.  One transition holds two observations: 17.6 KB at 54 x 54, so the reference's
+    default of 1e6 transitions takes 17.6 GB of device memory."""
+
+    def __init__(self, capacity: int, image_shape, n_internal: int, device):
+        self.capacity, self.device = int(capacity), device
+        self.img = torch.zeros((self.capacity,) + tuple(image_shape), dtype=torch.uint8, device=device)
+        self.next_img = torch.zeros_like(self.img)
+        self.internal = torch.zeros(self.capacity, n_internal, dtype=torch.float32, device=device)
+        self.next_internal = torch.zeros_like(self.internal)
+        self.actions = torch.zeros(self.capacity, dtype=torch.int64, device=device)
+        self.rewards = torch.zeros(self.capacity, dtype=torch.float32, device=device)
+        self.dones = torch.zeros(self.capacity, dtype=torch.float32, device=device)
+        self.pos, self.size = 0, 0
+
+    FIELDS = ("img", "next_img", "internal", "next_internal", "actions", "rewards", "dones")
+
+    def add(self, obs, next_obs, actions, rewards, dones) -> None:
+        n = obs["internal"].shape[0]
+        idx = (self.pos + torch.arange(n, device=self.device)) % self.capacity
+        self.img[idx], self.next_img[idx] = obs["external"], next_obs["external"]
+        self.internal[idx], self.next_internal[idx] = obs["internal"], next_obs["internal"]
+        self.actions[idx] = actions.to(torch.int64)
+        self.rewards[idx] = rewards.to(torch.float32)
+        self.dones[idx] = dones.to(torch.float32)
+        self.pos = (self.pos + n) % self.capacity
+        self.size = min(self.size + n, self.capacity)
+
+    def sample(self, n: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+        idx = torch.randint(0, self.size, (n,), device=self.device, generator=generator)
+        return dict(obs={"external": self.img[idx], "internal": self.internal[idx]}, actions=self.actions[idx],
+                    rewards=self.rewards[idx], next_obs={"external": self.next_img[idx], "internal": self.next_internal[idx]},
+                    dones=self.dones[idx])
+
+    def state_dict(self) -> Dict:
+        n = self.size
+        return dict(pos=self.pos, size=n, **{k: getattr(self, k)[:n].clone() for k in self.FIELDS})
+
+    def load_state_dict(self, src: Dict) -> None:
+        n = src["size"]
+        if n > self.capacity:
+            raise ValueError(f"checkpointed buffer holds {n} transitions, this buffer only {self.capacity}")
+        for k in self.FIELDS:
+            getattr(self, k)[:n] = src[k].to(self.device)
+        self.pos, self.size = src["pos"] % self.capacity, n
+
+
+def _clone_obs(obs):
+    return {k: v.clone() for k, v in obs.items()} if isinstance(obs, dict) else obs.clone()
+
+
 def exploration_rate(step: int, total: int, fraction: float = 0.2, initial: float = 1.0, final: float = 0.05) -> float:
     """SB3 ``get_linear_fn``: linear from ``initial`` to ``final`` over the first ``fraction`` of the run."""
     progress = step / float(total)
@@ -270,7 +322,9 @@ class DqnLearner:
     """Collect with an epsilon-greedy policy on a batched environment and update the Q-network.
 
     ``env`` needs ``B``, ``device``, ``reset()`` and ``step(actions, auto_reset=True)`` with the contract of
-    :class:`rl_env.BatchedRaysEnv`.  With ``torch.distributed`` initialised every rank drives its own shard of
+    :class:`rl_env.BatchedRaysEnv`.  On an image environment (``env.is_image_env``, :class:`rl_env.BatchedImgsEnv`) the
+    Q-network is :class:`dqn.ImageQNetwork`, observations stay dictionaries and the buffer keeps the images as uint8
+    (:class:`ImageReplayBuffer`); its update runs eagerly (``use_graph`` is refused).  With ``torch.distributed`` initialised every rank drives its own shard of
     environments and its own buffer; gradients are summed by :class:`DqnTrainer`'s single flat all-reduce."""
 
     def __init__(self, env, trainer: Optional[DqnTrainer] = None, buffer_size: int = 1_000_000,
@@ -280,9 +334,18 @@ class DqnLearner:
                  use_graph: bool = False, track_episodes: bool = True):
         self.env = env
         self.device = env.device
-        self.trainer = trainer if trainer is not None else DqnTrainer(device=str(self.device))
+        self.image = bool(getattr(env, "is_image_env", False))
+        if self.image and use_graph:
+            raise ValueError("use_graph=True is not built for the image environment: its updates run eagerly")
+        if trainer is None:
+            q_net = ImageQNetwork(env.image_shape) if self.image else None
+            trainer = DqnTrainer(q_net=q_net, device=str(self.device))
+        self.trainer = trainer
         self.trainer.target_update_interval = 0   # the learner syncs on environment steps, as SB3 does
-        self.buffer = ReplayBuffer(buffer_size, 46, self.device)
+        if self.image:
+            self.buffer = ImageReplayBuffer(buffer_size, env.image_shape, 14, self.device)
+        else:
+            self.buffer = ReplayBuffer(buffer_size, 46, self.device)
         self.learning_starts, self.batch_size, self.train_freq = learning_starts, batch_size, train_freq
         self.gradient_steps, self.target_update_interval = gradient_steps, target_update_interval
         self.eps = (exploration_fraction, exploration_initial_eps, exploration_final_eps)
@@ -302,9 +365,13 @@ class DqnLearner:
         self._obs, self._ep_return, self.n_updates = None, None, 0
         self._last_loss = torch.zeros((), device=self.device)
 
+    def _prepare(self, obs):
+        """The network's input: the flat vector for rays, the dictionary itself for images."""
+        return obs if self.image else flatten_observation(obs)
+
     def act(self, obs_flat: torch.Tensor, epsilon: float) -> torch.Tensor:
         greedy = self.trainer.q_net.greedy_actions(obs_flat)
-        B = obs_flat.shape[0]
+        B = greedy.shape[0]
         explore = torch.rand(B, device=self.device, generator=self.gen) < epsilon
         rand = torch.randint(0, 9, (B,), device=self.device, generator=self.gen)
         return torch.where(explore, rand, greedy)
@@ -320,9 +387,11 @@ class DqnLearner:
                  generator=self.gen.get_state(), episode_returns=list(self.episode_returns),
                  episode_successes=list(self.episode_successes), ep_count=self.ep_count.clone(),
                  ep_return_sum=self.ep_return_sum.clone(), ep_success_sum=self.ep_success_sum.clone(),
-                 obs=None if self._obs is None else self._obs.clone(),
+                 obs=None if self._obs is None else _clone_obs(self._obs),
                  ep_return=None if self._ep_return is None else self._ep_return.clone())
-        if include_buffer:
+        if include_buffer and self.image:
+            d["buffer"] = self.buffer.state_dict()
+        elif include_buffer:
             b, n = self.buffer, self.buffer.size
             d["buffer"] = dict(pos=b.pos, size=n, obs=b.obs[:n].clone(), next_obs=b.next_obs[:n].clone(),
                                actions=b.actions[:n].clone(), rewards=b.rewards[:n].clone(), dones=b.dones[:n].clone())
@@ -339,9 +408,16 @@ class DqnLearner:
         self.gen.set_state(d["generator"].cpu())   # a generator state is a host ByteTensor, also for a device generator
         self.episode_returns, self.episode_successes = list(d["episode_returns"]), list(d["episode_successes"])
         self.ep_count.copy_(d["ep_count"]); self.ep_return_sum.copy_(d["ep_return_sum"]); self.ep_success_sum.copy_(d["ep_success_sum"])
-        self._obs = None if d["obs"] is None else d["obs"].to(self.device)
+        if d["obs"] is None:
+            self._obs = None
+        elif self.image:
+            self._obs = {k: v.to(self.device) for k, v in d["obs"].items()}
+        else:
+            self._obs = d["obs"].to(self.device)
         self._ep_return = None if d["ep_return"] is None else d["ep_return"].to(self.device)
-        if "buffer" in d:
+        if "buffer" in d and self.image:
+            self.buffer.load_state_dict(d["buffer"])
+        elif "buffer" in d:
             b, src = self.buffer, d["buffer"]
             n = src["size"]
             if n > b.capacity:
@@ -369,7 +445,7 @@ class DqnLearner:
         point to checkpoint at; a later call, also on a learner restored with ``load``, continues exactly there."""
         env, B = self.env, self.env.B
         if self._obs is None:
-            self._obs = flatten_observation(env.reset())
+            self._obs = self._prepare(env.reset())
             self._ep_return = torch.zeros(B, dtype=torch.float64, device=self.device)
         obs, ep_return = self._obs, self._ep_return
         last_loss = self._last_loss
@@ -382,10 +458,10 @@ class DqnLearner:
                 actions = self.act(obs, eps)
                 nxt, reward, terminated, truncated, info = env.step(actions, auto_reset=True)
                 done = terminated | truncated
-                nxt_flat = flatten_observation(nxt)
+                nxt_flat = self._prepare(nxt)
                 # the transition stores the observation the episode ended in, not the first one of the next episode;
                 # a time-limit truncation is not a terminal state for the bootstrap (SB3 handle_timeout_termination)
-                stored_next = flatten_observation(info["terminal_observation"]) if "terminal_observation" in info else nxt_flat
+                stored_next = self._prepare(info["terminal_observation"]) if "terminal_observation" in info else nxt_flat
                 self.buffer.add(obs, stored_next, actions, reward, terminated)
                 ep_return += reward
                 if self.track_episodes:

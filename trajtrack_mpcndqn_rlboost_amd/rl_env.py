@@ -8,6 +8,9 @@ flags, sector / ray observation with memory, path observations, reward -- is ONE
 (``csrc/envgpu.hip``); this module only prepares the maps once (padded outlines, key frames, path lengths -> one record
 of doubles per environment) and keeps the state tensors.  torch is used for device memory only.
 
+``BatchedImgsEnv`` is the image-observation variant (``variants/imgs_reward1.py``): the same step kernel plus an image kernel
+(``csrc/envimg.hip``) that draws ``external`` as uint8 [B, 3, H, W].
+
 Maps and reference paths are inputs (the reference gets the path from ``extremitypathfinder``, a third-party A*;
 ``environment.py:124-147``).  There is no CPU path: without the built library and a HIP device construction raises.
 """
@@ -95,7 +98,14 @@ class _CParams(C.Structure):
                 ("angacc_max", C.c_double)]
 
 
-ENV_EXPORTS = ("mpcgpu_env_record_doubles", "mpcgpu_env_step_dev", "mpcgpu_env_step_autoreset_dev", "mpcgpu_env_last_error")
+class _CImgParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("down_sample", C.c_int32), ("reserved", C.c_int32),
+                ("scale_x", C.c_double), ("scale_y", C.c_double), ("center_x", C.c_double), ("center_y", C.c_double),
+                ("angle", C.c_double)]
+
+
+ENV_EXPORTS = ("mpcgpu_env_record_doubles", "mpcgpu_env_step_dev", "mpcgpu_env_step_autoreset_dev", "mpcgpu_env_last_error",
+               "mpcgpu_env_img_state_doubles", "mpcgpu_env_step_imgs_dev", "mpcgpu_env_step_imgs_autoreset_dev")
 
 
 def _bind(lib):
@@ -108,6 +118,13 @@ def _bind(lib):
     lib.mpcgpu_env_step_dev.restype = C.c_int32
     lib.mpcgpu_env_step_autoreset_dev.argtypes = [C.c_int32, C.POINTER(_CParams), C.c_int32] + [vp] * 10 + [C.c_int32, vp]
     lib.mpcgpu_env_step_autoreset_dev.restype = C.c_int32
+    ip = C.POINTER(_CImgParams)
+    lib.mpcgpu_env_img_state_doubles.argtypes = [ip]
+    lib.mpcgpu_env_img_state_doubles.restype = C.c_int32
+    lib.mpcgpu_env_step_imgs_dev.argtypes = [C.c_int32, C.POINTER(_CParams), ip, C.c_int32] + [vp] * 10
+    lib.mpcgpu_env_step_imgs_dev.restype = C.c_int32
+    lib.mpcgpu_env_step_imgs_autoreset_dev.argtypes = [C.c_int32, C.POINTER(_CParams), ip, C.c_int32] + [vp] * 12 + [C.c_int32, vp]
+    lib.mpcgpu_env_step_imgs_autoreset_dev.restype = C.c_int32
     lib.mpcgpu_env_last_error.argtypes = []
     lib.mpcgpu_env_last_error.restype = C.c_char_p
     lib._env_bound = True
@@ -329,3 +346,150 @@ class BatchedRaysEnv:
         """[B, 3] bool: collided with obstacle, collided with boundary, reached goal."""
         f = self.state[:, 7].to(self._torch.int64)
         return self._torch.stack([(f & 1) != 0, (f & 2) != 0, (f & 4) != 0], dim=1)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# image-observation variant (variants/imgs_reward1.py, components/ext_obsv_image.py)
+# ----------------------------------------------------------------------------------------------------------------------
+def image_params(width: int = 54, height: int = 54, scale_x: float = 1 / 18, scale_y: float = 1 / 18, down_sample: int = 2,
+                 center_x: float = 0.5, center_y: float = 0.3, angle: float = 0.0) -> _CImgParams:
+    """The image keyword arguments of ``TrajectoryPlannerEnvironmentImgsReward1`` (imgs_reward1.py:17-24) as the C struct."""
+    if down_sample != int(down_sample):
+        raise ValueError("only down_sample = 2 is built")
+    return _CImgParams(width=int(width), height=int(height), down_sample=int(down_sample), scale_x=scale_x, scale_y=scale_y,
+                       center_x=center_x, center_y=center_y, angle=angle)
+
+
+def image_distance_field(width: int = 54, height: int = 54, scale_x: float = 1 / 18, scale_y: float = 1 / 18,
+                         center_x: float = 0.5, center_y: float = 0.3) -> np.ndarray:
+    """Channel 2 of the image observation, uint8 [height, width]: ext_obsv_image.py:42-50, computed once on the host (it
+    depends on the image parameters only) and copied into every observation by the kernel."""
+    w = (width - 1) / (scale_x * width)
+    h = (height - 1) / (scale_y * height)
+    x, y = np.meshgrid(np.linspace(-w * center_x, w * (1 - center_x), width),
+                       np.linspace(-h * center_y, h * (1 - center_y), height))
+    distance = 2 / (1 + np.exp(-2 * np.sqrt(x ** 2 + y ** 2) / 10)) - 1   # components/utils.py:10-15
+    distance = distance - np.min(distance)
+    return (255.5 * (1 - distance / np.max(distance))).astype(np.uint8)
+
+
+class BatchedImgsEnv(BatchedRaysEnv):
+    """B independent ``TrajectoryPlannerEnvironmentImgsReward1`` environments (variants/imgs_reward1.py:7-49).
+
+    Robot, obstacles, internal observation, reward, flags and episode bookkeeping are those of :class:`BatchedRaysEnv`
+    (the same step kernel); the external observation is the image of ``components/ext_obsv_image.py``, uint8
+    ``[B, 3, H, W]``, drawn by a second kernel (``csrc/envimg.hip``): the padded boundary at 255 with the obstacles at 0,
+    at the current clock (channel 0) and at the oldest of the last 6 observations since the reset (channel 1), and the
+    constant distance field (channel 2).  Every observation pushes that history -- steps, ``observe()``, resets -- and a
+    reset clears it first (environment.py:161-180)."""
+
+    is_image_env = True
+
+    def __init__(self, maps: Sequence[Dict], device: int = 0, time_step: float = 0.2, max_episode_steps: int = 1000,
+                 sample_offset: float = 0.0, collision_factor: float = 4.0, reach_goal_factor: float = 3.0,
+                 cross_track_factor: float = 0.05, reference_speed: float = ROBOT["speed_max"] * 0.8,
+                 path_progress_factor: float = 2.0, image_width: int = 54, image_height: int = 54,
+                 image_scale_x: float = 1 / 18, image_scale_y: float = 1 / 18, image_down_sample: int = 2,
+                 image_center_x: float = 0.5, image_center_y: float = 0.3, image_angle: float = 0.0):
+        lib = _bind(load_library())
+        self.img_params = image_params(image_width, image_height, image_scale_x, image_scale_y, image_down_sample,
+                                       image_center_x, image_center_y, image_angle)
+        n_img = lib.mpcgpu_env_img_state_doubles(C.byref(self.img_params))
+        if n_img < 0:
+            raise ValueError(lib.mpcgpu_env_last_error().decode())
+        super().__init__(maps, device=device, time_step=time_step, max_episode_steps=max_episode_steps,
+                         sample_offset=sample_offset, collision_factor=collision_factor, reach_goal_factor=reach_goal_factor,
+                         cross_track_factor=cross_track_factor, reference_speed=reference_speed,
+                         path_progress_factor=path_progress_factor)
+        torch = self._torch
+        H, W = int(image_height), int(image_width)
+        self.image_shape = (3, H, W)
+        self.img_state = torch.zeros(self.B, n_img, dtype=torch.float64, device=self.device)
+        self.obs_image = torch.zeros(self.B, 3, H, W, dtype=torch.uint8, device=self.device)
+        self.term_image = torch.zeros_like(self.obs_image)
+        self.distance_field = torch.from_numpy(image_distance_field(W, H, image_scale_x, image_scale_y, image_center_x,
+                                                                    image_center_y)).to(self.device).contiguous()
+
+    def _launch(self, actions) -> None:
+        torch = self._torch
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        aptr = None
+        if actions is not None:
+            actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
+            if actions.shape != (self.B,):
+                raise ValueError(f"actions must have shape ({self.B},)")
+            aptr = actions.data_ptr()
+        rc = self._lib.mpcgpu_env_step_imgs_dev(self.device_index, C.byref(self.params), C.byref(self.img_params), self.B,
+                                                self.records.data_ptr(), self.state.data_ptr(), self.img_state.data_ptr(),
+                                                self.distance_field.data_ptr(), aptr, self.obs_internal.data_ptr(),
+                                                self.obs_image.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
+                                                stream)
+        if rc != 0:
+            raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
+
+    def _obs(self) -> Dict[str, "object"]:
+        return {"internal": self.obs_internal.clone(), "external": self.obs_image.clone()}
+
+    def reset(self, mask=None):
+        """Reset all (or the masked) environments to their map's start state and clear their image history.  The launch
+        that observes the reset rows observes every row, so the other rows' state, image history, observation, reward and
+        flag are restored afterwards: a partial reset leaves them bit-identical."""
+        torch = self._torch
+        if mask is None:
+            mask = torch.ones(self.B, dtype=torch.bool, device=self.device)
+        mask = torch.as_tensor(mask, device=self.device).bool()
+        fresh = torch.zeros_like(self.state)
+        fresh[:, :5] = self._start
+        fresh[:, 8:24] = self.state[:, 8:24]
+        self.state = torch.where(mask[:, None], fresh, self.state)
+        kept = (self.state.clone(), self.img_state.clone(), self.obs_internal.clone(), self.obs_image.clone(),
+                self.reward.clone(), self.terminated.clone())
+        self.img_state = torch.where(mask[:, None], torch.zeros_like(self.img_state), self.img_state)
+        self._launch(None)
+        self.state = torch.where(mask[:, None], self.state, kept[0])
+        self.state[:, 6] = torch.where(mask, torch.zeros_like(self.state[:, 6]), self.state[:, 6])
+        self.img_state = torch.where(mask[:, None], self.img_state, kept[1])
+        self.obs_internal.copy_(torch.where(mask[:, None], self.obs_internal, kept[2]))
+        self.obs_image.copy_(torch.where(mask[:, None, None, None], self.obs_image, kept[3]))
+        self.reward.copy_(torch.where(mask, self.reward, kept[4]))
+        self.terminated.copy_(torch.where(mask, self.terminated, kept[5]))
+        return self._obs()
+
+    def state_dict(self) -> Dict:
+        return dict(state=self.state.clone(), img_state=self.img_state.clone(), obs_internal=self.obs_internal.clone(),
+                    obs_image=self.obs_image.clone(), reward=self.reward.clone(), terminated=self.terminated.clone(),
+                    truncated=self.truncated.clone())
+
+    def load_state_dict(self, d: Dict) -> None:
+        for k in ("state", "img_state", "obs_internal", "obs_image", "reward", "terminated", "truncated"):
+            getattr(self, k).copy_(d[k].to(self.device))
+
+    def step(self, actions, auto_reset: bool = False):
+        """As :meth:`BatchedRaysEnv.step`; ``obs["external"]`` and ``info["terminal_observation"]["external"]`` are the
+        uint8 images."""
+        torch = self._torch
+        if not auto_reset:
+            self._launch(actions)
+            obs = self._obs()
+            terminated = self.terminated.bool()
+            truncated = (self.state[:, 25] >= self.max_episode_steps) & ~terminated
+            return obs, self.reward.clone(), terminated, truncated, {"success": (self.state[:, 7].to(torch.int64) & 4) != 0}
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
+        if actions.shape != (self.B,):
+            raise ValueError(f"actions must have shape ({self.B},)")
+        rc = self._lib.mpcgpu_env_step_imgs_autoreset_dev(
+            self.device_index, C.byref(self.params), C.byref(self.img_params), self.B, self.records.data_ptr(),
+            self.state.data_ptr(), self.img_state.data_ptr(), self.distance_field.data_ptr(), actions.data_ptr(),
+            self.obs_internal.data_ptr(), self.obs_image.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
+            self.truncated.data_ptr(), self.term_internal.data_ptr(), self.term_image.data_ptr(),
+            int(self.max_episode_steps), stream)
+        if rc != 0:
+            raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
+        obs = self._obs()
+        terminated, truncated = self.terminated.bool(), self.truncated.bool()
+        done = terminated | truncated
+        info = {"success": (self.state[:, 26].to(torch.int64) & 4) != 0,
+                "terminal_observation": {"internal": torch.where(done[:, None], self.term_internal, obs["internal"]),
+                                         "external": torch.where(done[:, None, None, None], self.term_image, obs["external"])}}
+        return obs, self.reward.clone(), terminated, truncated, info
