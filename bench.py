@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: batched receding-horizon NMPC solves on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing more: it generates the scenes, warms up, times the K steps,
+writes `--dump-outputs` if asked and prints the JSON line (with a `roofline` object whose counter-based fields come from the
+committed passes, `measured_in_run: false`).  Everything else -- the side legs, the counter passes, the CPU baseline -- runs
+with `--full` only (see below); `--full` adds objects to the line and leaves the headline leg, which runs first, as it is.
 
 `--dump-outputs DIR` writes, after the timed steps, what the headline leg's last timed step returned (u, cost, status,
 inner_it, outer_it, f2norm) as DIR/<name>.npy in float64, at most 64 MB in all (beyond that a fixed, seeded sample of rows,
@@ -28,15 +33,16 @@ torch.distributed.run as a CHILD process -- before anything here has touched the
 child's code.  It exits non-zero when fewer than N devices are present, and when WORLD_SIZE disagrees with
 --gpus.
 
-Rank 0 prints ONE JSON line (contract in the task description) with extra objects:
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) with extra objects:
   roofline      -- dominant kernel (solve_kernel) against the HBM roofline, timed with HIP events on the launch
                    stream IN THIS RUN; `flops` is the executed f64 flop rate from the in-kernel evaluation counters
-                   of this run.  What needs hardware counters (`traffic`, `secondary`) is measured in this run as well
+                   of this run.  What needs hardware counters (`traffic`, `secondary`) is measured in a --full run as well
                    when rocprofv3 is there (N = 1): after the timed legs, three `rocprofv3 --pmc` passes (SQ counters,
                    FETCH_SIZE, WRITE_SIZE: one pass each, never combined with a trace) over a child bench.py on the
-                   same parameter vectors, rebuilt by tools/roofline.py -- `measured_in_run: true`.  Without the
-                   profiler (or with --no-pmc) the fields come from profiles/r06_roofline_bench.json -- the committed
+                   same parameter vectors, rebuilt by tools/roofline.py -- `measured_in_run: true`.  Otherwise (a plain
+                   run, no profiler, --no-pmc, N > 1) the fields come from profiles/r06_roofline_bench.json -- the committed
                    passes on this very workload -- and are marked `measured_in_run: false` with the reason.
+The objects below come with --full only.
   config.convergent -- the same step on the "passing" scene family (same N, obstacle counts and batch; a
                    collision-free plan exists), where about half of the solves converge: the headline family is the
                    one SURVEY.md 8(d) prescribes and it is cap-limited (see status_histogram).
@@ -63,8 +69,9 @@ Rank 0 prints ONE JSON line (contract in the task description) with extra object
                    the call that is not the solve kernels (copies + synchronisation).
   psi_evals_per_s -- psi evaluations per second of the headline leg: the workload-independent rate (families with other iteration
                    counts compare on it).
-  The side legs (convergent, avoidance, ordered, batch_sweep, closed_loop, counter passes, cpu_baseline) run with ONE rank only
-  (world == 1) unless --full is given: an N-rank run is the headline leg and nothing else.
+  The side legs (convergent, avoidance, ordered, batch_sweep, other_stall_reading, host_boundary, closed_loop) run on every rank of
+  an N-rank --full run; the counter passes and cpu_baseline on a one-rank --full run only.  A plain run, of any N, is the headline
+  leg and nothing else.
   cpu_baseline  -- the oracle (plain-C restatement, "port") on the host cores this process may use, on a bounded
                    sample.  Its answers double as the checker of THIS run: `cpu_baseline.parity_on_sample` compares the control
                    sequences the timed launches wrote for the same problems (converged pairs: max |du| against the 1e-3 tolerance;
@@ -121,7 +128,9 @@ def parse_args(argv=None):
     ap.add_argument("--penalty-stall", choices=("either", "both"), default=None,
                     help="reading of the ALM penalty-stall rule (default: the yaml / library default)")
     ap.add_argument("--side-batch", type=int, default=32768, help="problems per GPU of the convergent / avoidance legs")
-    ap.add_argument("--full", action="store_true", help="run the side legs on every rank of a multi-GPU run as well")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg, run everything else as well: side legs (on every rank of a multi-GPU run), "
+                         "counter passes and CPU baseline (one-rank run); a plain run is the headline leg only")
     ap.add_argument("--p-file", default=None, help=argparse.SUPPRESS)   # counter passes: the parent's parameter vectors (.npy)
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64)")
@@ -428,12 +437,13 @@ def main():
         p = family_on_device("benchmark", B, 1234 + 7919 * rank)
         sc = {"p": None}            # the host copy is reused by the other families; cpu_baseline / counter passes read p back
     gen_s = time.perf_counter() - t_gen
-    side = world == 1 or args.full   # side legs: one rank (or --full)
+    side = args.full                 # side legs: --full only (on every rank of an N-rank run)
+    cpu_leg = args.full and args.cpu_seconds > 0 and world == 1 and not stub
     leg = timed_leg(p, args.steps, args.warmup)
     if args.dump_outputs:   # before any other leg reuses `out`; rank r > 0 of an N-rank run writes rank<r>_<name>.npy
         dump_outputs(args.dump_outputs, out, DUMP_BUDGET_BYTES // world, prefix=f"rank{rank}_" if rank else "")
     # the control sequences of the first problems of the headline batch, for the parity figures next to the CPU baseline (below)
-    head_u = None if stub else out["u"][:16384].cpu().numpy().copy()
+    head_u = out["u"][:16384].cpu().numpy().copy() if cpu_leg else None
     elapsed, per_rank_s = over_ranks(leg["elapsed"])
 
     def ordered_leg(pb, steps, sv=None, o=None):
@@ -633,8 +643,8 @@ def main():
             "config": {"workload": f"mpc_default.yaml N_hor={N}, {args.n_dyn} dynamic obstacles (r=1.6 m discs crossing "
                                    "the path, SURVEY.md 8(d)), 5 static boxes, cold start u0=0, "
                                    f"batch={B} robots per GPU; K plain launches on one stream, problems started in the order given "
-                                   "(config.ordered: the library's default order; batch_sweep: the reference batches 32768 and "
-                                   "8192, plain / ordered / pipelined)",
+                                   "(with --full, config.ordered_perfect_hints: the library's default order; batch_sweep: the reference "
+                                   "batches 32768 and 8192, plain / ordered / pipelined)",
                        "batch_per_gpu": B, "N_hor": N, "n_dyn": args.n_dyn, "parallelism": f"shard{world}",
                        "penalty_stall": getattr(cfg, "solver_penalty_stall", "either"),
                        "mean_inner_iterations": float(inner.mean()),
@@ -696,8 +706,12 @@ def main():
         if not stub:
             from tools.roofline import flops_per_solve_kernel_launch, load_pmc_for
             pmc = load_pmc_for(ROOFLINE_JSON, N, args.n_dyn, B)
-            p_host = sc["p"] if sc["p"] is not None else p.cpu().numpy()
-            pmc_here, pmc_err = (None, "disabled (--no-pmc)") if (args.no_pmc or world > 1) else pmc_in_run(args, p_host)
+            if not args.full:
+                pmc_here, pmc_err = None, "plain run: the counter passes run with --full"
+            elif args.no_pmc or world > 1:
+                pmc_here, pmc_err = None, "disabled (--no-pmc)" if args.no_pmc else "disabled (an N-rank run)"
+            else:
+                pmc_here, pmc_err = pmc_in_run(args, sc["p"] if sc["p"] is not None else p.cpu().numpy())
             in_run = pmc_here is not None
             if in_run:
                 pmc = pmc_here
@@ -741,7 +755,7 @@ def main():
                                      "source": "this run: rocprofv3 --pmc SQ_* pass over a child bench.py" if in_run
                                                else os.path.relpath(ROOFLINE_JSON, ROOT)}
             line["roofline"] = roof
-        if args.cpu_seconds > 0 and world == 1 and not stub:
+        if cpu_leg:
             line["cpu_baseline"] = cpu_baseline(cfg, p[:16384].cpu().numpy(), args.cpu_seconds, gpu_u=head_u, gpu_status=leg["status"][:16384],
                                                 family_samples={f: v["sample"] for f, v in side_legs.items() if "sample" in v})
         print(json.dumps(line), flush=True)

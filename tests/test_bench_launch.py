@@ -48,6 +48,27 @@ def test_multi_rank_run_without_full_is_bounded_by_the_headline_leg():
         assert k not in line["config"], k
 
 
+def test_one_rank_run_is_the_headline_leg_unless_full():
+    """A plain one-rank run is the headline leg and nothing else; --full adds the side legs after it."""
+    runs = {}
+    for extra in ([], ["--full"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64"] + extra,
+                           env=_env(MPCGPU_BENCH_STUB="1"), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        runs[bool(extra)] = json.loads(lines[0])
+    plain, full = runs[False], runs[True]
+    for line in (plain, full):
+        assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["data"] == "stub"
+        assert abs(line["value"] - 64 * 2 / (line["ms_per_step"] * 2e-3)) < 1e-6 * line["value"]
+    for k in ("convergent", "avoidance", "batch_sweep", "closed_loop", "ordered_perfect_hints", "other_stall_reading", "host_boundary"):
+        assert k not in plain["config"], k
+    assert full["config"]["convergent"]["value"] > 0 and full["config"]["avoidance"]["value"] > 0
+    assert "ordered_perfect_hints" in full["config"]
+    assert set(plain) == set(full) and set(plain["config"]) < set(full["config"])   # --full adds objects to config, nothing else
+
+
 def test_bench_refuses_a_world_size_that_disagrees_with_gpus():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--batch", "8"],
                        env=_env(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", MPCGPU_BENCH_STUB="1"), capture_output=True,

@@ -1,5 +1,6 @@
 """bench.py on the GPU at a small batch: the JSON line carries the contract's fields, `roofline` is consistent with the
-run's own HIP-event kernel time, and the counter-based fields are measured in the run when rocprofv3 is there."""
+run's own HIP-event kernel time, and the counter-based fields are measured in a --full run when rocprofv3 is there.  A plain
+run is the headline leg only."""
 import json
 import os
 import shutil
@@ -16,7 +17,7 @@ pytestmark = pytest.mark.gpu
 def test_bench_line_contract_and_in_run_counters():
     B = 4096
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(B), "--steps", "2", "--warmup", "1",
-                        "--cpu-seconds", "2", "--no-sweep", "--no-closed-loop"], cwd=ROOT, stdout=subprocess.PIPE,
+                        "--cpu-seconds", "2", "--no-sweep", "--no-closed-loop", "--full"], cwd=ROOT, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -66,11 +67,39 @@ def test_bench_line_contract_and_in_run_counters():
         assert ro["traffic"] is None and ro["secondary"] is None and not ro["measured_in_run"]["secondary"]
 
 
+def test_plain_run_is_the_headline_leg_only(tmp_path):
+    """Without --full: the contract's fields, the roofline of this run's kernel time (counter fields from the committed passes or
+    null, never measured in the run) and the dumped outputs of the last timed step -- no side leg, no counter pass, no CPU baseline."""
+    import numpy as np
+    B = 4096
+    d_out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(B), "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(d_out)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline"):
+        assert k in d, k
+    assert d["unit"] == "solves/s" and d["dtype"] == "f64" and d["higher_is_better"] is True and d["steps"] == 2
+    assert abs(d["value"] - B * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+    assert "cpu_baseline" not in d
+    for k in ("convergent", "avoidance", "batch_sweep", "metric_batch", "ordered_perfect_hints", "other_stall_reading",
+              "host_boundary", "closed_loop"):
+        assert k not in d["config"], k
+    ro = d["roofline"]
+    assert ro["kernel_ms"] <= d["ms_per_step"] * 1.001 and ro["measured_in_run"]["kernel_ms"]
+    assert ro["measured_in_run"]["traffic"] is False and "--full" in ro["traffic_source"]
+    assert sum(d["config"]["status_histogram"]) == B
+    st = np.load(d_out / "status.npy")
+    assert st.shape == (B,) and np.array_equal(np.bincount(st.astype(np.int64), minlength=3), d["config"]["status_histogram"])
+
+
 def test_two_ranks_share_the_one_gpu_through_the_real_solver():
     """The N > 1 path of bench.py with the REAL library: two rank processes (started by bench.py itself, gloo for the barrier and
     the reductions) shard the batch and share the one GPU of this box -- what the driver's 8-GPU run does with one GPU per rank.
     Each rank solves its own B robots (weak scaling); the line reports both ranks' rates and the whole-job value over the
-    max-over-ranks time; side legs stay on the one-rank run."""
+    max-over-ranks time; side legs come with --full only."""
     B = 4096
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["MPCGPU_BENCH_BACKEND"] = "gloo"

@@ -6,7 +6,7 @@ mkdir -p $O
 # the tables below are those of rounds 1-5: problems started in the order given (bench.py sets the order of each of its legs itself);
 # the library's default order gets a table of its own at the end
 export MPCGPU_ORDER=as_given
-python bench.py --steps 5 --warmup 1 > $O/bench_line.json 2> $O/bench.err
+python bench.py --steps 5 --warmup 1 --full > $O/bench_line.json 2> $O/bench.err
 (echo "# tools/phase_prof.py on a -DMPC_PROFILE build of the final source of this round (throughput kernel; shader-clock cycles per phase; 16 resident wavefronts per CU at N = 20, 12 at N = 40)"; MPCGPU_LIB=$PWD/build_ab/libmpcgpu_prof.so python tools/phase_prof.py 8192 20; MPCGPU_LIB=$PWD/build_ab/libmpcgpu_prof.so python tools/phase_prof.py 4096 40) > $O/phase_table.txt 2>&1
 (echo "# config 2: N_hor = 20, 4 dynamic obstacles, B = 1024 (tools/prof_solve.py 1024 3 4 20)"; python tools/prof_solve.py 1024 3 4 20; echo "# config 3: N_hor = 40, 8 dynamic obstacles, B = 4096 / 16384 (tools/prof_solve.py B 3 8 40)"; python tools/prof_solve.py 4096 3 8 40; python tools/prof_solve.py 16384 2 8 40) > $O/config2_config3.txt 2>&1
 (echo "# tools/prof_solve.py B 2 8 20: benchmark scene family, N_hor = 20, 8 dynamic obstacles, cold start, solve kernel ms"; for B in 8192 16384 32768 65536 131072; do python tools/prof_solve.py $B 2 8 20; done) > $O/batch_scaling.txt 2>&1
