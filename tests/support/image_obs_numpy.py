@@ -179,13 +179,19 @@ def obstacle_world(ob: Dict, clock: float) -> np.ndarray:
 
 
 def to_pixels(world: np.ndarray, pose, ip: ImageParams):
-    """(int pixels [n, 2], distance of every coordinate before truncation to the nearest integer [n, 2])."""
+    """(int pixels [n, 2], distance of every coordinate before the clamp and the truncation to the nearest value where
+    its pixel would change [n, 2]).
+
+    Away from the clamp that is the nearest integer.  A coordinate beyond +-2^20 px clamps to 2^20 on either side of a
+    last-ulp difference, so only its distance to the clamp itself counts (the clamped value would otherwise always
+    count as exactly on an integer)."""
     c, s = math.cos(pose[2] - ip.angle), math.sin(pose[2] - ip.angle)
     dx, dy = world[:, 0] - pose[0], world[:, 1] - pose[1]
     px = (2.0 * ip.width) * (ip.scale_x * (s * dx - c * dy) + ip.center_x)
     py = (2.0 * ip.height) * (ip.scale_y * (c * dx + s * dy) + ip.center_y)
-    raw = np.clip(np.stack([px, py], axis=1), -PIX_CLAMP, PIX_CLAMP)
-    return np.trunc(raw).astype(np.int64), np.abs(raw - np.round(raw))
+    raw = np.stack([px, py], axis=1)
+    near = np.where(np.abs(raw) >= PIX_CLAMP, np.abs(raw) - PIX_CLAMP, np.abs(raw - np.round(raw)))
+    return np.trunc(np.clip(raw, -PIX_CLAMP, PIX_CLAMP)).astype(np.int64), near
 
 
 def render_pair(spec: Dict, pose, clock0: float, clock1: float, ip: ImageParams, dfield: Optional[np.ndarray] = None,

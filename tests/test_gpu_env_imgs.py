@@ -3,7 +3,8 @@ restatement of tests/support/image_obs_numpy.py.  Images must equal the restatem
 truncation to integer pixels is integer arithmetic.  The restatement is driven by the kernel's own robot pose and clock
 (float64, bit-identical to the ray variant's), so what is compared is the image rule alone.  Only images with a vertex
 within 1e-9 px of an integer before truncation are exempt (there a last-ulp difference of a libm cos / sin may move a
-vertex across the boundary); the random-state test reports how many and bounds them."""
+vertex across the boundary; a coordinate clamped to +-2^20 px counts by its distance to the clamp); the random-state test
+reports how many and bounds them."""
 import ctypes as C
 import importlib
 import json

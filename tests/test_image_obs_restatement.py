@@ -69,6 +69,30 @@ def test_vertex_truncation_toward_zero():
     assert pix.tolist() == [[1, -1]]           # 1.2 -> 1, -1.2 -> -1
 
 
+def test_ambiguity_is_measured_before_the_clamp():
+    """A coordinate beyond +-2^20 px clamps to the same pixel whatever its last ulp: only its distance to the clamp makes
+    it ambiguous, not the integer it is clamped to.  Inside the clamp the distance to the nearest integer counts."""
+    ip = im.ImageParams(width=8, height=8, scale_x=1.0, scale_y=1.0, center_x=0.0, center_y=0.0, angle=math.pi / 2)
+    # theta - angle = 0: pixel x = 16 * (-dy), pixel y = 16 * dx, every product exact
+    world = np.array([[65536.5, 0.0],        # y = 2^20 + 8: clamped, 8 px beyond the clamp
+                      [-70000.0, 0.0],       # y = -1 120 000: clamped to -2^20
+                      [65536.0, 0.0],        # y = 2^20 exactly: a smaller value would truncate to 2^20 - 1
+                      [0.03125, 0.0],        # y = 0.5
+                      [100.0, -0.25]])       # y = 1600, x = 4: on integers
+    pix, near = im.to_pixels(world, (0.0, 0.0, math.pi / 2), ip)
+    assert pix[:, 1].tolist() == [2 ** 20, -2 ** 20, 2 ** 20, 0, 1600] and pix[:, 0].tolist() == [0, 0, 0, 0, 4]
+    assert near[:, 1].tolist() == [8.0, 70000.0 * 16 - 2 ** 20, 0.0, 0.5, 0.0]
+    eps = 1e-9
+    assert (near[:, 1] < eps).tolist() == [False, False, True, False, True]
+    # a boundary with clamped corners and no vertex near an integer is drawn and not exempt
+    spec = {"boundary_padded": np.array([[-1e5, -1e5 + 0.3], [1e5, -1e5 + 0.3], [1e5, 1e5 + 0.3], [-1e5, 1e5 + 0.3]]),
+            "obstacles": []}
+    bpix, bnear = im.to_pixels(spec["boundary_padded"], (0.3, 0.2, math.pi / 2), ip)
+    assert (np.abs(bpix) == 2 ** 20).all() and (bnear > 1.0).all()
+    img, amb = im.render_pair(spec, (0.3, 0.2, math.pi / 2), 0.0, 0.0, ip)
+    assert not amb and (img[:2] == 255).all()
+
+
 def test_closed_form_line_equals_the_stepwise_walk():
     rng = np.random.default_rng(3)
     for _ in range(400):
