@@ -71,6 +71,7 @@ def main():
     ap.add_argument("--gradient-steps", type=int, default=16)
     ap.add_argument("--batch-size", type=int, default=256)
     ap.add_argument("--double-q", action="store_true")
+    ap.add_argument("--per", action="store_true", help="prioritized experience replay (device-resident sum tree; the reference's 'per': True)")
     ap.add_argument("--graph", action="store_true", help="replay the update from captured HIP graphs (multi-rank: two graphs around the all-reduce)")
     ap.add_argument("--save", default=None, help="directory for best_model.pt / final_model.pt / checkpoint.pt")
     ap.add_argument("--resume", default=None, help="checkpoint.pt of an earlier run with the same arguments")
@@ -92,7 +93,7 @@ def main():
     learner = dqn_train.DqnLearner(env, trainer, buffer_size=2_000_000, learning_starts=4 * args.envs,
                                    batch_size=args.batch_size, train_freq=4, gradient_steps=args.gradient_steps,
                                    target_update_interval=200_000, exploration_fraction=0.3, use_graph=args.graph,
-                                   track_episodes=False)
+                                   track_episodes=False, per=args.per)
     ck_name = "checkpoint.pt" if rank == 0 else f"checkpoint.rank{rank}.pt"
     if args.resume:
         learner.load(args.resume if rank == 0 else os.path.join(os.path.dirname(args.resume), ck_name))
@@ -141,7 +142,8 @@ def main():
                                          ("one HIP graph" if args.graph else "eager"),
                           "config": {"workload": "BASELINE.json config 5 (scene 1, medium box, periodic obstacle)",
                                      "envs_per_gpu": args.envs, "timesteps_per_gpu": int(stats["timesteps"]),
-                                     "batch_size": args.batch_size, "gradient_steps": args.gradient_steps, "double_q": bool(args.double_q)},
+                                     "batch_size": args.batch_size, "gradient_steps": args.gradient_steps, "double_q": bool(args.double_q),
+                                     "per": bool(args.per)},
                           "success_rate": stats["success_rate"], "mean_return": stats["mean_return"]}))
     if world > 1:
         dist.destroy_process_group()

@@ -18,6 +18,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from .dqn import ImageQNetwork, QNetwork
+from .per_tree import SumTree
 
 
 class DqnTrainer:
@@ -90,7 +91,8 @@ class DqnTrainer:
                 raise AssertionError(f"Q-network replicas differ across ranks (max |diff| {float((hi - lo).abs().max()):.3e})")
 
     def update(self, batch: Dict[str, torch.Tensor]) -> float:
-        """batch (this rank's shard): obs [b,46] f32, actions [b] i64, rewards [b], next_obs [b,46], dones [b]."""
+        """batch (this rank's shard): obs [b,46] f32, actions [b] i64, rewards [b], next_obs [b,46], dones [b]; with
+        ``weights`` [b] f32 (prioritized replay) the loss is weighted per row and ``last_td_error`` [b] holds the TD errors."""
         loss = self._eager_step(batch)
         self.num_updates += 1
         if self.target_update_interval and self.num_updates % self.target_update_interval == 0:
@@ -99,12 +101,13 @@ class DqnTrainer:
 
     # ---- hipGraph path: the update is ~40 tiny kernels (MLP forward / backward, Huber loss, clip, Adam) on 1 177
     # parameters, i.e. pure launch latency; captured once, it replays as ONE graph launch
-    def enable_graph(self, batch_size: int, obs_dim: int = 46) -> None:
+    def enable_graph(self, batch_size: int, obs_dim: int = 46, weighted: bool = False) -> None:
         """Capture ``update`` for a fixed batch size into HIP graphs (``torch.cuda.CUDAGraph`` is hipGraph on ROCm).
         One process: ONE graph.  Several ranks: TWO graphs with the flat-bucket all-reduce between them -- graph A =
         forward, backward and packing the gradients into the bucket; the collective (RCCL) is enqueued eagerly on the same
         stream; graph B = averaging, unpacking, clipping and the Adam step.  Every rank must call this (the warm-up steps
-        contain collectives)."""
+        contain collectives).  ``weighted``: the captured update takes a static ``weights`` input and leaves the TD errors
+        in the static tensor ``last_td_error`` (prioritized replay)."""
         dev = self._bucket.device
         if dev.type != "cuda":
             raise RuntimeError("enable_graph needs the GPU")
@@ -113,6 +116,8 @@ class DqnTrainer:
         self._g_batch = dict(obs=torch.zeros(batch_size, obs_dim, device=dev), actions=torch.zeros(batch_size, dtype=torch.int64, device=dev),
                              rewards=torch.zeros(batch_size, device=dev), next_obs=torch.zeros(batch_size, obs_dim, device=dev),
                              dones=torch.zeros(batch_size, device=dev))
+        if weighted:
+            self._g_batch["weights"] = torch.ones(batch_size, device=dev)
         self._g_loss = torch.zeros((), device=dev)
         keep_interval, self.target_update_interval = self.target_update_interval, 0
         state = ([p.detach().clone() for p in self._params], self.num_updates)
@@ -145,7 +150,13 @@ class DqnTrainer:
     def _backward(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
         target = self.td_target(batch["rewards"], batch["next_obs"], batch["dones"])
         q = self.q_net(batch["obs"]).gather(1, batch["actions"].view(-1, 1)).squeeze(1)
-        loss = F.smooth_l1_loss(q, target)
+        if "weights" in batch:
+            # prioritized replay: mean(w_i * huber(delta_i)), every row weighted by ITS importance weight, and the TD errors
+            # delta = target - Q(s, a) kept on the device for the re-prioritization (deviation 3)
+            self.last_td_error = (target - q).detach()
+            loss = (batch["weights"] * F.smooth_l1_loss(q, target, reduction="none")).mean()
+        else:
+            loss = F.smooth_l1_loss(q, target)
         self.optimizer.zero_grad(set_to_none=False)
         loss.backward()
         return loss.detach()
@@ -253,7 +264,9 @@ class ReplayBuffer:
         self.size = min(self.size + n, self.capacity)
 
     def sample(self, n: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
-        idx = torch.randint(0, self.size, (n,), device=self.device, generator=generator)
+        return self._rows(torch.randint(0, self.size, (n,), device=self.device, generator=generator))
+
+    def _rows(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
         return dict(obs=self.obs[idx], actions=self.actions[idx], rewards=self.rewards[idx],
                     next_obs=self.next_obs[idx], dones=self.dones[idx])
 
@@ -288,7 +301,9 @@ class ImageReplayBuffer:
         self.size = min(self.size + n, self.capacity)
 
     def sample(self, n: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
-        idx = torch.randint(0, self.size, (n,), device=self.device, generator=generator)
+        return self._rows(torch.randint(0, self.size, (n,), device=self.device, generator=generator))
+
+    def _rows(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
         return dict(obs={"external": self.img[idx], "internal": self.internal[idx]}, actions=self.actions[idx],
                     rewards=self.rewards[idx], next_obs={"external": self.next_img[idx], "internal": self.next_internal[idx]},
                     dones=self.dones[idx])
@@ -304,6 +319,64 @@ class ImageReplayBuffer:
         for k in self.FIELDS:
             getattr(self, k)[:n] = src[k].to(self.device)
         self.pos, self.size = src["pos"] % self.capacity, n
+
+
+class _Prioritized:
+    """Prioritized experience replay on top of a ring buffer: the priorities of the stored transitions are the leaves of a
+    device-resident sum tree (:class:`per_tree.SumTree`, csrc/pergpu.hip).  Keyword names are the reference's
+    (``PerReplayBuffer``, src/pkg_dqn/utils/per_dqn.py:43-56); ``refresh_tree_freq`` is accepted and ignored -- inner nodes
+    here are always the sum of their children and never drift."""
+
+    def _init_tree(self, alpha=0.3, beta=0.4, epsilon=1e-3, update_max_freq=1_000, refresh_tree_freq=50_000,
+                   initial_priority=1):
+        self.sum_tree = SumTree(self.capacity, self.device, alpha=alpha, beta=beta, epsilon=epsilon,
+                                update_max_freq=update_max_freq, initial_priority=initial_priority)
+
+    def add(self, obs, next_obs, actions, rewards, dones) -> None:
+        n = actions.shape[0]
+        self.sum_tree.add(self.pos, n, self.size)      # the new rows take the running maximum priority
+        super().add(obs, next_obs, actions, rewards, dones)
+
+    def sample(self, n: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+        """Stratified by priority.  The usual batch plus ``indices`` (tree indices, for :meth:`update_priorities`) and
+        ``weights`` (importance weights, float32, normalised by their maximum)."""
+        u = torch.rand(n, dtype=torch.float64, device=self.device, generator=generator)
+        indices, positions, weights = self.sum_tree.sample(u, self.size)
+        batch = self._rows(positions)
+        batch["indices"], batch["weights"] = indices, weights
+        return batch
+
+    def update_priorities(self, indices: torch.Tensor, td_error: torch.Tensor) -> None:
+        self.sum_tree.update(indices, td_error)
+
+    def state_dict(self) -> Dict:
+        n = self.size
+        d = dict(pos=self.pos, size=n, **{k: getattr(self, k)[:n].clone() for k in self.FIELDS})
+        d["per"] = self.sum_tree.state_dict(n)
+        return d
+
+    def load_state_dict(self, src: Dict) -> None:
+        n = src["size"]
+        if n > self.capacity:
+            raise ValueError(f"checkpointed buffer holds {n} transitions, this buffer only {self.capacity}")
+        for k in self.FIELDS:
+            getattr(self, k)[:n] = src[k].to(self.device)
+        self.pos, self.size = src["pos"] % self.capacity, n
+        self.sum_tree.load_state_dict(src["per"])
+
+
+class PrioritizedReplayBuffer(_Prioritized, ReplayBuffer):
+    FIELDS = ("obs", "next_obs", "actions", "rewards", "dones")
+
+    def __init__(self, capacity: int, obs_dim: int, device, **per_kwargs):
+        ReplayBuffer.__init__(self, capacity, obs_dim, device)
+        self._init_tree(**per_kwargs)
+
+
+class PrioritizedImageReplayBuffer(_Prioritized, ImageReplayBuffer):
+    def __init__(self, capacity: int, image_shape, n_internal: int, device, **per_kwargs):
+        ImageReplayBuffer.__init__(self, capacity, image_shape, n_internal, device)
+        self._init_tree(**per_kwargs)
 
 
 def _clone_obs(obs):
@@ -331,7 +404,12 @@ class DqnLearner:
                  learning_starts: int = 50_000, batch_size: int = 32, train_freq: int = 4, gradient_steps: int = -1,
                  target_update_interval: int = 10_000, exploration_fraction: float = 0.2,
                  exploration_initial_eps: float = 1.0, exploration_final_eps: float = 0.05, seed: int = 0,
-                 use_graph: bool = False, track_episodes: bool = True):
+                 use_graph: bool = False, track_episodes: bool = True, per: bool = False,
+                 per_kwargs: Optional[Dict] = None):
+        """``per=True``: prioritized experience replay (the reference's ``'per': True``): the buffer keeps a sum tree of
+        priorities (``per_kwargs``: alpha, beta, epsilon, update_max_freq, initial_priority), minibatches are drawn by
+        priority, the loss is weighted by the importance weights and the drawn rows are re-prioritized with their TD errors
+        after every update -- all on the device.  With several ranks every rank has its own tree."""
         self.env = env
         self.device = env.device
         self.image = bool(getattr(env, "is_image_env", False))
@@ -342,7 +420,12 @@ class DqnLearner:
             trainer = DqnTrainer(q_net=q_net, device=str(self.device))
         self.trainer = trainer
         self.trainer.target_update_interval = 0   # the learner syncs on environment steps, as SB3 does
-        if self.image:
+        self.per = bool(per)
+        if self.per and self.image:
+            self.buffer = PrioritizedImageReplayBuffer(buffer_size, env.image_shape, 14, self.device, **(per_kwargs or {}))
+        elif self.per:
+            self.buffer = PrioritizedReplayBuffer(buffer_size, 46, self.device, **(per_kwargs or {}))
+        elif self.image:
             self.buffer = ImageReplayBuffer(buffer_size, env.image_shape, 14, self.device)
         else:
             self.buffer = ReplayBuffer(buffer_size, 46, self.device)
@@ -360,7 +443,10 @@ class DqnLearner:
         self.ep_success_sum = torch.zeros((), dtype=torch.float64, device=self.device)
         self.use_graph = use_graph
         if use_graph:
-            self.trainer.enable_graph(batch_size)
+            if self.per:
+                self.trainer.enable_graph(batch_size, weighted=True)
+            else:
+                self.trainer.enable_graph(batch_size)
         # state of the collection loop between two learn() calls (a run can be checkpointed and resumed in the middle)
         self._obs, self._ep_return, self.n_updates = None, None, 0
         self._last_loss = torch.zeros((), device=self.device)
@@ -389,7 +475,7 @@ class DqnLearner:
                  ep_return_sum=self.ep_return_sum.clone(), ep_success_sum=self.ep_success_sum.clone(),
                  obs=None if self._obs is None else _clone_obs(self._obs),
                  ep_return=None if self._ep_return is None else self._ep_return.clone())
-        if include_buffer and self.image:
+        if include_buffer and (self.image or self.per):
             d["buffer"] = self.buffer.state_dict()
         elif include_buffer:
             b, n = self.buffer, self.buffer.size
@@ -415,7 +501,7 @@ class DqnLearner:
         else:
             self._obs = d["obs"].to(self.device)
         self._ep_return = None if d["ep_return"] is None else d["ep_return"].to(self.device)
-        if "buffer" in d and self.image:
+        if "buffer" in d and (self.image or self.per):
             self.buffer.load_state_dict(d["buffer"])
         elif "buffer" in d:
             b, src = self.buffer, d["buffer"]
@@ -485,7 +571,10 @@ class DqnLearner:
                 steps = self.gradient_steps if self.gradient_steps >= 0 else collected
                 for _ in range(steps):
                     step = self.trainer.update_graphed if self.use_graph else self.trainer.update
-                    last_loss = step(self.buffer.sample(self.batch_size, self.gen))
+                    batch = self.buffer.sample(self.batch_size, self.gen)
+                    last_loss = step(batch)
+                    if self.per:      # the PER kernels run eagerly on the same stream, around the (possibly replayed) update
+                        self.buffer.update_priorities(batch["indices"], self.trainer.last_td_error)
                 n_updates += steps
             self._obs, self._ep_return, self.n_updates, self._last_loss = obs, ep_return, n_updates, last_loss
             if callback is not None:
