@@ -12,7 +12,9 @@ of doubles per environment) and keeps the state tensors.  torch is used for devi
 (``csrc/envimg.hip``) that draws ``external`` as uint8 [B, 3, H, W].
 
 Maps and reference paths are inputs (the reference gets the path from ``extremitypathfinder``, a third-party A*;
-``environment.py:124-147``).  There is no CPU path: without the built library and a HIP device construction raises.
+``environment.py:124-147``); ``path_plan.plan_reference_paths`` plans them on the GPU for drawn maps
+(:func:`random_dynamic_spec`), and :meth:`BatchedRaysEnv.replace_maps` puts new maps into a running environment.  There is no
+CPU path: without the built library and a HIP device construction raises.
 """
 from __future__ import annotations
 
@@ -86,6 +88,29 @@ def make_map(boundary, static: Sequence, dynamic: Sequence[Dict], start, goal, p
                 boundary_padded=rg.buffer_polygon(_f32(rg.orient(boundary)), -radius), obstacles=obstacles)
 
 
+def random_dynamic_spec(rng) -> Dict:
+    """``generate_map_dynamic`` (utils/map.py:158-189) on a numpy ``Generator``: a 40 x 20 m hall, three static boxes and
+    seven periodic obstacles, start on x = 5 and goal on x = 35.  The same distributions in the same order of draws, not
+    the same stream as Python's ``random``.  Returns the keyword form of :func:`make_map` without ``path`` (the boxes may
+    overlap and may cross the boundary; ``path_plan.plan_reference_paths`` plans a path or says there is none)."""
+    start = [5.0, float(rng.uniform(5, 15)), float(rng.uniform(0, 2 * math.pi)), 0.0, 0.0]
+    static, dynamic = [], []
+    for i in range(10):
+        x, y = float(rng.uniform(10, 30)), float(rng.uniform(0, 20))
+        if i < 3:
+            w = max(4.0, float(rng.uniform(0, 0.5 * min(x - 10, 30 - x))))
+            h = max(4.0, float(rng.uniform(0, min(y, 20 - y))))
+            x0, y0 = x - w / 2, y - h / 2
+            static.append([(x0, y0), (x0 + w, y0), (x0 + w, y0 + h), (x0, y0 + h)])
+        else:
+            x2, y2 = x + float(rng.uniform(-5, 5)), y + float(rng.uniform(-5, 5))
+            rx, ry = float(rng.uniform(0.2, 1.2)), float(rng.uniform(0.2, 1.2))
+            freq, angle = float(rng.uniform(0.3, 0.7)), float(rng.uniform(0, 2 * math.pi))
+            dynamic.append(dict(p1=(x, y), p2=(x2, y2), freq=freq, rx=rx, ry=ry, angle=angle))
+    return dict(boundary=[(0.0, 0.0), (40.0, 0.0), (40.0, 20.0), (0.0, 20.0)], static=static, dynamic=dynamic, start=start,
+                goal=[35.0, float(rng.uniform(5, 15))])
+
+
 class _CParams(C.Structure):
     _fields_ = [("n_path_max", C.c_int32), ("n_obst_max", C.c_int32), ("n_kf_max", C.c_int32), ("n_edge_max", C.c_int32),
                 ("num_segments", C.c_int32), ("corner_samples", C.c_int32),
@@ -142,12 +167,21 @@ def path_lengths(path: np.ndarray):
     return cum, seg
 
 
-def pack_records(maps: Sequence[Dict], n_kf_max: int = 2):
-    """maps -> (records [B, R] float64, dict of the batch maxima P, M, K, E); layout: include/mpcgpu_env.h."""
+def pack_records(maps: Sequence[Dict], n_kf_max: int = 2, limits: Optional[Dict] = None):
+    """maps -> (records [B, R] float64, dict of the batch maxima P, M, K, E); layout: include/mpcgpu_env.h.
+
+    ``limits`` (``n_path_max``, ``n_obst_max``, ``n_kf_max``, ``n_edge_max`` of an existing record table) packs the maps
+    into THAT table's layout instead of the batch's own, and raises if a map does not fit."""
     P = max(2, max(len(m["path"]) for m in maps))
     M = max(len(m["obstacles"]) for m in maps)
     K = max([n_kf_max] + [len(o["keyframes"]) for m in maps for o in m["obstacles"]])
     E = max(len(m["boundary_padded"]) + sum(len(o["padded_nodes"]) for o in m["obstacles"]) for m in maps)
+    if limits is not None:
+        need = dict(n_path_max=P, n_obst_max=M, n_kf_max=K, n_edge_max=E)
+        over = [f"{k} {need[k]} > {limits[k]}" for k in need if need[k] > limits[k]]
+        if over:
+            raise ValueError("a map does not fit the record table: " + ", ".join(over))
+        P, M, K, E = (int(limits[k]) for k in ("n_path_max", "n_obst_max", "n_kf_max", "n_edge_max"))
     if P > 64 or M > 31 or K > 4:
         raise ValueError("limits: at most 64 path nodes, 31 obstacles, 4 key frames per obstacle")
     an = 4 + (K + 1) + 3 * K
@@ -227,6 +261,25 @@ class BatchedRaysEnv:
         self.term_external = torch.zeros_like(self.obs_external)
         self.max_episode_steps = max_episode_steps
         self.time_step = time_step
+
+    def replace_maps(self, rows, maps: Sequence[Dict]) -> None:
+        """Give environments ``rows`` the new ``maps`` (:func:`make_map`, e.g. with a path of ``path_plan``): their rows
+        of the device record table are re-packed in place, no other row is touched.  Raises ``ValueError``, before
+        anything is written, if a map exceeds the table's ``n_path_max``, ``n_obst_max``, ``n_kf_max`` or
+        ``n_edge_max``.  The rows keep their state until a following ``reset(mask)`` starts them on the new maps."""
+        torch = self._torch
+        rows = [int(r) for r in rows]
+        if len(rows) != len(maps) or len(set(rows)) != len(rows) or any(r < 0 or r >= self.B for r in rows):
+            raise ValueError(f"replace_maps needs one map per row, rows distinct and in [0, {self.B})")
+        if not rows:
+            return
+        limits = {k: getattr(self.params, k) for k in ("n_path_max", "n_obst_max", "n_kf_max", "n_edge_max")}
+        rec, _ = pack_records(maps, limits=limits)
+        assert rec.shape[1] == self.records.shape[1]
+        idx = torch.as_tensor(rows, dtype=torch.int64, device=self.device)
+        start = np.stack([np.asarray(m["start"], dtype=np.float64) for m in maps])
+        self.records[idx] = torch.from_numpy(rec).to(self.device)
+        self._start[idx] = torch.from_numpy(start).to(self.device)
 
     # ---- kernel launch ---------------------------------------------------------------------------------------------
     def _launch(self, actions) -> None:

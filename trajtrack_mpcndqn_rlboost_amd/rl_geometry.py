@@ -112,6 +112,59 @@ def buffer_polygon(ring: Sequence[Sequence[float]], distance: float, quad_segs: 
     return res
 
 
+def mitre_polygon(ring: Sequence[Sequence[float]], distance: float, mitre_limit: float = 2.0, check: bool = True) -> np.ndarray:
+    """Offset a simple polygon by ``distance`` (> 0 grows, < 0 shrinks) with mitred joins; returns the open CCW ring.
+
+    Restates ``Polygon.buffer(distance, join_style=mitre, mitre_limit=mitre_limit)`` as the reference's path planning uses
+    it (``obstacle.py:177-185,248-256``) with the same *local* construction as :func:`buffer_polygon`: every edge is moved
+    by ``distance`` along its normal and neighbouring offset edges are intersected.  A corner that opens on the offset
+    side and whose mitre would reach further than ``mitre_limit * |distance|`` from its vertex is bevelled instead: cut
+    by the line perpendicular to the corner's bisector at that distance (two points, on the first and on the second
+    offset edge).  Raises when the offset ring is not simple (an edge vanished, two parts of the outline met)."""
+    poly = orient(ring, ccw=True)
+    n = len(poly)
+    if n < 3:
+        raise ValueError("a polygon needs at least three vertices")
+    if distance == 0.0:
+        return poly
+    r = abs(distance)
+    sgn = 1.0 if distance > 0 else -1.0
+    limit = mitre_limit * r
+    out = []
+    for i in range(n):
+        v = poly[i]
+        d0 = v - poly[i - 1]
+        d1 = poly[(i + 1) % n] - v
+        d0 = d0 / math.sqrt(d0[0] * d0[0] + d0[1] * d0[1])
+        d1 = d1 / math.sqrt(d1[0] * d1[0] + d1[1] * d1[1])
+        n0 = sgn * np.array([d0[1], -d0[0]])
+        n1 = sgn * np.array([d1[1], -d1[0]])
+        turn = d0[0] * d1[1] - d0[1] * d1[0]
+        c = float(n0[0] * n1[0] + n0[1] * n1[1])
+        if abs(turn) < 1e-14 and c > 0:          # collinear: one offset point
+            out.append(v + r * n0)
+            continue
+        if c <= -1.0 + 1e-14:
+            raise ValueError("a ring that doubles back on itself has no mitred offset")
+        # |r (n0 + n1) / (1 + c)| = r sqrt(2 / (1 + c))
+        if turn * sgn > 0 and r * math.sqrt(2.0 / (1.0 + c)) > limit:
+            m = n0 + n1
+            m = m / math.sqrt(m[0] * m[0] + m[1] * m[1])
+            t = np.array([-m[1], m[0]])
+            for nk in (n0, n1):
+                s = (r - limit * float(m[0] * nk[0] + m[1] * nk[1])) / float(t[0] * nk[0] + t[1] * nk[1])
+                out.append(v + limit * m + s * t)
+        else:
+            out.append(v + r * (n0 + n1) / (1.0 + c))
+    res = np.asarray(out)
+    if check:
+        if signed_area(res) <= 0 or not ring_is_simple(res):
+            raise ValueError("mitred ring intersects itself: the local offset construction does not apply to this polygon")
+        if distance < 0 and not all(point_in_ring(p, poly) for p in res):
+            raise ValueError("shrunk mitred ring leaves the polygon: the local offset construction does not apply")
+    return res
+
+
 def point_in_ring(pt, ring: np.ndarray) -> bool:
     """Even-odd rule (points exactly on the outline are a measure-zero case the reference does not rely on)."""
     x, y = float(pt[0]), float(pt[1])
