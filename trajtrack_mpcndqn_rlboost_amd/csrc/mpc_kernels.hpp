@@ -192,9 +192,21 @@ enum { YS_C = 0, YS_GAMMA, YS_IG, YS_LIP, YS_SIGMA, YS_COST, YS_GG, YS_D2H, YS_A
        YS_ALMIT, YS_NOUTER, YS_INNERTOT, YS_STATUS, YS_NEVAL, YS_NEVALG, YS_LBACTIVE, YS_LBHEAD, YS_TRN, YS_TRPSI, YS_SCALARS = 32 };
 constexpr int YS_VECW = 8;
 __host__ __device__ constexpr int yield_even_c(int x) { return (x + 1) & ~1; }
+// The step body of the Gram form (PanocLbfgsGram::update / ::direction) trimmed to its arithmetic for the compiled shape N_hor = 20,
+// memory 10: y_i.y_j stored SQUARE like s_i.y_j (both recurrences read row_base[sp]: no triangular index per iteration and lane),
+// the pass-1 operands and the row coefficients staged with one guarded store each, lane roles formed with 24-bit arithmetic.
+// Same FMA sequence, same bits.  0 = the form of round 6 (`make variants`: libmpcgpu_step_r6.so, the bitwise yardstick of
+// tests/test_gpu_lean_step.py).  The square matrix costs 360 B of LDS: N_hor = 20 has them below its 8 granules (10 008 of
+// 10 240 B, sixteen wavefronts per compute unit), N_hor = 40 does not (12 624 of 12 800 B) and keeps the packed form.
+// Looked at so far: the instruction stream of the cross-compiled kernel only (profiles/lean_step_dynamic_mix_N20.txt); the runs
+// on the MI355X against the parent build that profiles/lean_step_ab.txt lists have not been made.
+#ifndef MPC_LEAN_STEP
+#define MPC_LEAN_STEP 1
+#endif
+__host__ __device__ constexpr bool gram_square(int N, int mem) { return MPC_LEAN_STEP && N == 20 && mem == 10; }
 // doubles of the LDS region `gg` (Gram matrices, or the alpha scratch of the two-loop form): see fixed_lds
 __host__ __device__ constexpr int gg_doubles_c(int N, int mem, bool gram) {
-    return gram ? yield_even_c(mem * mem + mem * (mem + 1) / 2) : yield_even_c(mem);
+    return gram ? yield_even_c(mem * mem + (gram_square(N, mem) ? mem * mem : mem * (mem + 1) / 2)) : yield_even_c(mem);
 }
 
 // How H * (gamma fpr) is evaluated: 1 = Gram form (PanocLbfgsGram, round 3), 0 = two-loop recursion (PanocLbfgs; the build
@@ -280,8 +292,8 @@ __host__ __device__ constexpr FixedLds fixed_lds(int N, int mem, bool lbfgs_in_l
     { const int ps = part_doubles_c(N, mem); o += ps > 2 * HW_ROWS ? ps : 2 * HW_ROWS; }
     f.bal = o; o += bal_doubles_c(N, mem);
     f.rho = o; o += even_c(mem);
-    f.gg = o;   // Gram matrices s_i.y_j (full) + y_i.y_j (packed symmetric), or the alpha scratch of the two-loop form
-    o += gram_shape(N, mem) ? even_c(mem * mem + mem * (mem + 1) / 2) : even_c(mem);
+    f.gg = o;   // Gram matrices s_i.y_j (full) + y_i.y_j (packed symmetric; square where gram_square), or the alpha scratch of the two-loop form
+    o += gg_doubles_c(N, mem, gram_shape(N, mem));
     f.S = f.Y = f.old = o;
     if (lbfgs_in_lds) {
         f.S = o; o += mem * N * 2;
@@ -1825,7 +1837,8 @@ struct LbMem {
     double* LOLD;   // [N][4]: previous (u, gamma fpr)
     double* LRHO;   // [mem]
     double* LALPHA; // [mem]        two-loop form only
-    double* GG;     // Gram form only: [mem][mem] s_i.y_j (slot indices), then y_i.y_j packed symmetric: entry (i >= j) at i(i+1)/2 + j
+    double* GG;     // Gram form only: [mem][mem] s_i.y_j (slot indices), then y_i.y_j -- packed symmetric: entry (i >= j) at i(i+1)/2 + j; where
+                    // gram_square (the lean step body, N_hor = 20): square [mem][mem] like s_i.y_j, both halves written
     double* XA;     // Gram form only: scratch, see PanocLbfgsGram
 };
 
@@ -2017,7 +2030,9 @@ struct PanocLbfgsGram {
         // pass-1 operands of this lane: its row of [S; Y], chunk g of the row's (v, w) pairs -- CL consecutive pairs (the last
         // chunk runs into the next row, or into the zero row that follows the last one: a finite value times the zero padding
         // of XA).  The OLD rows do not depend on the new pair: with a compile-time shape they are requested before anything else.
+        constexpr bool SQ = gram_square(NT, MEMT);   // lean step body (MPC_LEAN_STEP): y_i.y_j square, staging as the shape needs it
         asm volatile("" : "+v"(lane));  // opaque: the per-lane addresses are rebuilt here, not hoisted out of the solver loop (and spilled)
+        if (SQ) __builtin_assume(lane >= 0 && lane < WAVE);   // ... with 24-bit multiplies and no sign extensions
         const Role ro = role(D, lane);
         const int row_a = ro.isy * mem + ro.slot_a;
         const double2* mrow = reinterpret_cast<const double2*>(m.LM + (row_a * N + ro.g * D.CL) * 2);
@@ -2034,10 +2049,18 @@ struct PanocLbfgsGram {
             s0 = uv - LOLD[lane * 4]; s1 = uw - LOLD[lane * 4 + 1];
             y0_ = rv - LOLD[lane * 4 + 2]; y1_ = rw - LOLD[lane * 4 + 3];
         }
-        for (int k = lane; k < D.G * D.CL; k += WAVE) {  // slots N .. G*CL-1 pad the last chunk with zeros
-            double2* x = reinterpret_cast<double2*>(m.XA + k * 4);
-            const bool real = vl && k == lane;
-            x[0] = make_double2(real ? rv : 0.0, real ? rw : 0.0); x[1] = make_double2(real ? y0_ : 0.0, real ? y1_ : 0.0);
+        if (SQ) {   // G * CL <= 64 chunk slots: one store per lane, and y_new is zero beyond the vector lanes already
+            static_assert(!SQ || ((WAVE / 2) / (MEMT ? MEMT : 1)) * CLT <= WAVE, "one chunk slot per lane");
+            if (lane < D.G * D.CL) {
+                double2* x = reinterpret_cast<double2*>(m.XA + lane * 4);
+                x[0] = make_double2(vl ? rv : 0.0, vl ? rw : 0.0); x[1] = make_double2(y0_, y1_);
+            }
+        } else {
+            for (int k = lane; k < D.G * D.CL; k += WAVE) {  // slots N .. G*CL-1 pad the last chunk with zeros
+                double2* x = reinterpret_cast<double2*>(m.XA + k * 4);
+                const bool real = vl && k == lane;
+                x[0] = make_double2(real ? rv : 0.0, real ? rw : 0.0); x[1] = make_double2(real ? y0_ : 0.0, real ? y1_ : 0.0);
+            }
         }
         double ys, ss;
         P::sum2(__builtin_fma(s0, y0_, s1 * y1_), __builtin_fma(s0, s0, s1 * s1), ys, ss);
@@ -2096,7 +2119,15 @@ struct PanocLbfgsGram {
             // Column h of both Gram matrices from the totals of pass 1; row h of s_i.y_j is zero (s_new is newer than every y),
             // and so is its diagonal.  The rows of slot h itself held the pair that is being replaced: what they contribute is
             // overwritten right after -- the LDS writes of a wavefront keep their order.
-            if (ro.slot < mem && ro.g == D.G - 1) {
+            if (SQ) {
+                // both matrices square: the lane of row (isy, slot) writes entry (slot, h) of its matrix, the y-rows (h, slot) too
+                if (ro.slot < mem && ro.g == D.G - 1) {
+                    double* gr = m.GG + row_a * mem;
+                    gr[h] = ay;
+                    if (ro.isy) m.GG[(mem + h) * mem + ro.slot] = ay;
+                    if (ro.slot == h) pr = ro.isy ? yr : sr;
+                }
+            } else if (ro.slot < mem && ro.g == D.G - 1) {
                 if (!ro.isy) {
                     m.GG[ro.slot * mem + h] = ay;                  // s_q . y_new
                     if (ro.slot == h) pr = sr;
@@ -2108,7 +2139,7 @@ struct PanocLbfgsGram {
             wave_sync();
             if (lane < mem) m.GG[h * mem + lane] = zero_here();   // (a hoisted 0.0 sat in a spill slot and came back from scratch in every step)
             if (lane == 0) {
-                m.GG[mem * mem + yy_index(h, h)] = yy;
+                m.GG[mem * mem + (SQ ? h * mem + h : yy_index(h, h))] = yy;
                 m.LRHO[h] = 1.0 / ys;
             }
             hgamma = P::uni(ys / yy);
@@ -2122,7 +2153,9 @@ struct PanocLbfgsGram {
         if (active == 0) { dv = rv; dw = rw; return; }
         const Dims<NT, MEMT> D(kp);
         const int N = D.N, mem = D.mem;
+        constexpr bool SQ = gram_square(NT, MEMT);
         asm volatile("" : "+v"(lane));  // opaque, see update()
+        if (SQ) __builtin_assume(lane >= 0 && lane < WAVE);
         const Role ro = role(D, lane);
         double* COEF = m.XA + D.xa_len();  // [G2 * CR] coefficients of the rows (zero beyond the active pairs)
         // pass-2 operands: lane = g2 * N + k2 takes rows g2 * CR .. (the row after the last one is the zero row); they depend on
@@ -2146,19 +2179,27 @@ struct PanocLbfgsGram {
             for (int tt = 0; tt < CRT; ++tt) mq[tt] = mcol[tt * N];
         }
         // first loop, newest pair first: alpha_p = rho_p s_p.q_p; every row's product with q advances by -alpha_p (row . y_p)
-        // s-rows read row slot of s_i.y_j; y-rows read entry (slot, sp) of the packed symmetric y_i.y_j
-        const double* gs = m.GG + ro.slot_a * mem;
-        const double* gy = m.GG + mem * mem;
-        const int tri_l = ro.slot_a * (ro.slot_a + 1) / 2;
-        auto g1 = [&](int sp) { return ro.isy ? gy[sp <= ro.slot_a ? tri_l + sp : sp * (sp + 1) / 2 + ro.slot_a] : gs[sp]; };
+        // s-rows read row slot of s_i.y_j; y-rows read entry (slot, sp) of y_i.y_j: row slot of the square matrix (lean step body), or
+        // the triangular index of the packed one
+        const double* grow = m.GG + (ro.isy * mem + ro.slot_a) * mem;   // row (isy, slot) of either square matrix (the s-rows' in both forms)
+        auto g1 = [&](int sp) {
+            if constexpr (SQ) {
+                return grow[sp];
+            } else {
+                const double* gy = m.GG + mem * mem;
+                const int tri_l = ro.slot_a * (ro.slot_a + 1) / 2;
+                return ro.isy ? gy[sp <= ro.slot_a ? tri_l + sp : sp * (sp + 1) / 2 + ro.slot_a] : grow[sp];
+            }
+        };
         double acc = pr;
         {
-            int sp = head;
+            int sp = SQ ? __builtin_amdgcn_readfirstlane(head) : head;   // ring position on the scalar unit, like the second loop
             double gnext = g1(sp);
             for (int p = 0; p < active; ++p) {
                 const double gcur = gnext;
                 const int sl = sp * D.G + D.G - 1;
                 sp = sp + 1 >= mem ? 0 : sp + 1;
+                if (SQ) sp = __builtin_amdgcn_readfirstlane(sp);
                 gnext = g1(sp);   // one step ahead of the broadcast that needs it
                 const double al = readlane_d(rho_l * acc, sl);
                 acc = __builtin_fma(-al, gcur, acc);

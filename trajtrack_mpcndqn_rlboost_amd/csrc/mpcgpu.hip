@@ -310,7 +310,7 @@ void fill_team_layout(KParams& k, int tw, int mKs, int mKf, int mKd) {
     k.l_rho = o; o += even(k.mem);
     k.l_alpha = o;
     k.l_gg = o;
-    if (gram_layout(k)) o += even(k.mem * k.mem + k.mem * (k.mem + 1) / 2); else o += even(k.mem);
+    o += gg_doubles_c(k.N, k.mem, gram_layout(k));
     k.l_old = o; o += N * 4;
     k.l_wstride = even(o - base);
     k.l_total = base + tw * k.l_wstride;
