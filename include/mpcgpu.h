@@ -121,6 +121,11 @@ int32_t mpcgpu_solve_batch_dev(void* handle, int32_t B, const double* p, const d
 int32_t mpcgpu_cost_grad_batch(void* handle, int32_t B, const double* u, const double* xi, const double* p,
                                double* psi, double* f, double* grad, double* F1, double* F2);
 
+/* Test hook (added within ABI 8) -- psi alone, through the value-only form of the evaluation: the code the Lipschitz test of the
+ * solve kernel's step loop runs (no gradient partial is formed).  Same inputs as mpcgpu_cost_grad_batch; psi [B] is bitwise the
+ * psi of that call.  HOST pointers. */
+int32_t mpcgpu_psi_value_batch(void* handle, int32_t B, const double* u, const double* xi, const double* p, double* psi);
+
 /* Device time (ms, HIP events on the launch stream) of the last solve call: parameter-compaction kernel and
  * solve kernel.  Valid after the stream has been synchronised. */
 int32_t mpcgpu_last_timing(void* handle, double* prep_ms, double* solve_ms);

@@ -198,12 +198,20 @@ __host__ __device__ constexpr int yield_even_c(int x) { return (x + 1) & ~1; }
 // Same FMA sequence, same bits.  0 = the form of round 6 (`make variants`: libmpcgpu_step_r6.so, the bitwise yardstick of
 // tests/test_gpu_lean_step.py).  The square matrix costs 360 B of LDS: N_hor = 20 has them below its 8 granules (10 008 of
 // 10 240 B, sixteen wavefronts per compute unit), N_hor = 40 does not (12 624 of 12 800 B) and keeps the packed form.
-// Looked at so far: the instruction stream of the cross-compiled kernel only (profiles/lean_step_dynamic_mix_N20.txt); the runs
-// on the MI355X against the parent build that profiles/lean_step_ab.txt lists have not been made.
+// Instruction stream of the cross-compiled kernel: profiles/lean_step_dynamic_mix_N20.txt; on the MI355X against the 0 build
+// (profiles/lean_step_ab.txt): -2.5 % VALU instructions per solve, -2.7 % kernel time on the benchmark leg.
 #ifndef MPC_LEAN_STEP
 #define MPC_LEAN_STEP 1
 #endif
 __host__ __device__ constexpr bool gram_square(int N, int mem) { return MPC_LEAN_STEP && N == 20 && mem == 10; }
+// The Lipschitz test of the step loop (solve_body) evaluates psi(u_half) through the value-only form of eval_point (its template
+// parameter VO): no gradient partial is formed on the item lanes or carried through LDS for a number that only feeds a comparison.
+// Same psi, bit for bit; same carve.  0 = the general form with want_grad = false as a literal (`make variants`:
+// libmpcgpu_vo0.so, the bitwise yardstick and A/B partner: tests/test_gpu_value_only.py, profiles/value_only_ab.txt).
+// On the MI355X against the 0 build: -1.40 % VALU instructions per solve, -1.5 % kernel time on the benchmark leg.
+#ifndef MPC_VALUE_ONLY
+#define MPC_VALUE_ONLY 1
+#endif
 // doubles of the LDS region `gg` (Gram matrices, or the alpha scratch of the two-loop form): see fixed_lds
 __host__ __device__ constexpr int gg_doubles_c(int N, int mem, bool gram) {
     return gram ? yield_even_c(mem * mem + (gram_square(N, mem) ? mem * mem : mem * (mem + 1) / 2)) : yield_even_c(mem);
@@ -1044,9 +1052,17 @@ struct SegDist {
 // ------------------------------------------------------------------------------------------------
 // psi(u; c, y), f(u), F1, F2 and (optionally) grad psi at the point held by the vector lanes.
 // ------------------------------------------------------------------------------------------------
-template <int NT, bool SC, class P, bool AXIS = false, bool LIN = false, int MINW = 3>
+// VO (value only): psi alone, decided at compile time -- the form of the Lipschitz test of the step loop (solve_body), which reads
+// nothing but the number psi(u_half).  want_grad and want_f are false by definition; beyond what they switch off, the item lanes
+// form no gradient partial (nearest-point gradient, fleet, polygon and soft-ellipse terms), the lanes of sub >= 1 park only their
+// segment minimum, the vector lane folds only that minimum (exact in any order: no tie walk), and the stash keeps only (v, w).
+// Everything psi is made of -- cost_l, S_l, the hinge row sums, F2e, F2pad, vcost, dist_l, the one wave reduction, F1a / F1b --
+// keeps its expressions and their order: the same bits as the general form (tests/test_gpu_value_only.py).  The carve is the
+// general form's (PARTW, stash stride): LDS bytes and residency do not move.
+template <int NT, bool SC, class P, bool AXIS = false, bool LIN = false, int MINW = 3, bool VO = false>
 __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, double v, double w, double c, double icm,
-                                           double ya, double yb, bool want_grad, bool want_f, EvalOut& out PROF_ARG) {
+                                           double ya, double yb, bool want_grad_, bool want_f_, EvalOut& out PROF_ARG) {
+    const bool want_grad = !VO && want_grad_, want_f = !VO && want_f_;
     const int N = NT ? NT : kp.N;
     int lane = cx.lane;
     asm volatile("" : "+v"(lane));  // opaque: per-lane LDS addresses are rebuilt here instead of being hoisted out
@@ -1124,7 +1140,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
     {
     const double Cx = (c0 + 4.0 * cm + c2) * sixth, Sy = (s0 + 4.0 * sm + s2) * sixth;
     const double dCw = -ts * (2.0 * sm + s2) * sixth, dSw = ts * (2.0 * cm + c2) * sixth;
-    if (STW == 0) { kCx = Cx; kSy = Sy; kdCw = dCw; kdSw = dSw; }
+    if (STW == 0 && !VO) { kCx = Cx; kSy = Sy; kdCw = dCw; kdSw = dSw; }
     double pX, pY;
     // lanes beyond the horizon carry v = 0 and finite phasors: their increments are (signed) zeros without a select, and an
     // inclusive PREFIX never reads them into a vector lane
@@ -1141,7 +1157,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
         // that they do not occupy registers across the item loops
         if (STW >= 4) {
             double* st = cx.stash + lane * STW;
-            st[0] = Cx; st[1] = Sy; st[2] = dCw; st[3] = dSw;
+            if (!VO) { st[0] = Cx; st[1] = Sy; st[2] = dCw; st[3] = dSw; }
             if (STW == 6) { st[4] = v; st[5] = w; }
         }
     }
@@ -1206,7 +1222,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
             const SegDist sd(sg, px, py);
             if (sd.d2 < best) {
                 best = sd.d2;
-                sd.grad(bgx, bgy);
+                if (!VO) sd.grad(bgx, bgy);
             }
         }
         // (2) every later segment of this lane lies in the bounding circle stored with segment i (the circle of ALL segments
@@ -1229,7 +1245,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
                 if (sd.d2 < best) {
                     best = sd.d2;
                     sb = sqrt_upper(sd.d2, KC(K_SQRT));
-                    sd.grad(bgx, bgy);
+                    if (!VO) sd.grad(bgx, bgy);
                 }
                 i += LPS;
                 more = false;
@@ -1248,8 +1264,10 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
             const double hh = kp.W2 - (ex * ex + ey * ey);
             if (hh > 0.0) {
                 cost_l += fleetw * hh;
-                gx -= 2.0 * fleetw * ex;
-                gy -= 2.0 * fleetw * ey;
+                if (!VO) {
+                    gx -= 2.0 * fleetw * ex;
+                    gy -= 2.0 * fleetw * ey;
+                }
             }
         }
         // static polygons, 4 half-planes each (mpc_generator.py:219-225,46-54)
@@ -1267,10 +1285,12 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
             const double prod = p01 * p23;
             if (prod > 0.0) {
                 S_l += prod;
-                const double r0 = 2.0 * m0 * q1 * p23, r1 = 2.0 * m1 * q0 * p23;
-                const double r2 = 2.0 * m2 * q3 * p01, r3 = 2.0 * m3 * q2 * p01;
-                dsx -= r0 * s[4] + r1 * s[5] + r2 * s[6] + r3 * s[7];
-                dsy -= r0 * s[8] + r1 * s[9] + r2 * s[10] + r3 * s[11];
+                if (!VO) {
+                    const double r0 = 2.0 * m0 * q1 * p23, r1 = 2.0 * m1 * q0 * p23;
+                    const double r2 = 2.0 * m2 * q3 * p01, r3 = 2.0 * m3 * q2 * p01;
+                    dsx -= r0 * s[4] + r1 * s[5] + r2 * s[6] + r3 * s[7];
+                    dsy -= r0 * s[8] + r1 * s[9] + r2 * s[10] + r3 * s[11];
+                }
             }
         }
         PROF_MARK(3);  // fleet + static
@@ -1293,7 +1313,8 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
                 if (Is > 0.0) {
                     cost_l += d.wgt * Is * Is;
                     const double wI = 2.0 * d.wgt * Is;
-                    if (!foreign) {   // the expressions of the row walk, term for term
+                    if (VO) {         // value only: the cost term is all there is
+                    } else if (!foreign) {   // the expressions of the row walk, term for term
                         if (AXIS) {
                             gx += wI * (-2.0 * d.a * d.isx);
                             gy += wI * (2.0 * d.b * d.isy);
@@ -1363,7 +1384,8 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
             if (Is > 0.0) {
                 cost_l += d.wgt * Is * Is;
                 const double wI = 2.0 * d.wgt * Is;
-                if (AXIS) {   // the general terms with cos = 1, sin = 0: the products by 1 are exact, those by 0 vanish
+                if (VO) {     // value only: the cost term is all there is
+                } else if (AXIS) {   // the general terms with cos = 1, sin = 0: the products by 1 are exact, those by 0 vanish
                     gx += wI * (-2.0 * d.a * d.isx);
                     gy += wI * (2.0 * d.b * d.isy);
                 } else {
@@ -1558,11 +1580,22 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
     //      (sub 0): its partial stays in registers, only the lanes of sub >= 1 go through LDS.
     if (c_il && c_isub > 0) {
         double* pp = cx.part + ((c_isub - 1) * N + c_ik) * PARTW;
-        pp[0] = gx; pp[1] = gy; pp[2] = best; pp[3] = bgx; pp[4] = bgy;
+        if (VO) pp[2] = best;   // the slot of the general form: same carve
+        else { pp[0] = gx; pp[1] = gy; pp[2] = best; pp[3] = bgx; pp[4] = bgy; }
     }
     wave_sync();
     double Gx = Gpx, Gy = Gpy, vcost = 0.0;
-    if (c_vl) {
+    if (VO) {
+        if (c_vl) {   // the minimum alone, folded by the comparisons of the general form
+            double bb = inf;
+            if (best < bb) bb = best;
+            for (int s = 1; s < LPS; ++s) {
+                const double b2 = cx.part[((s - 1) * N + lane) * PARTW + 2];
+                if (b2 < bb) bb = b2;
+            }
+            vcost = HD(H_QRPD) * bb;
+        }
+    } else if (c_vl) {
         double bb = inf, wbx = 0.0, wby = 0.0;
         bool tie = false;
         Gx += gx; Gy += gy;
@@ -1627,10 +1660,12 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
         if (lane == N - 1) {
             const double ex = X - HD(H_XG), ey = Y - HD(H_YG), et = thN - HD(H_THG);
             vcost += HD(H_QN) * (ex * ex + ey * ey) + HD(H_QTHN) * et * et;
-            Gx += 2.0 * HD(H_QN) * ex; Gy += 2.0 * HD(H_QN) * ey;
-            gthN = 2.0 * HD(H_QTHN) * et;
+            if (!VO) {
+                Gx += 2.0 * HD(H_QN) * ex; Gy += 2.0 * HD(H_QN) * ey;
+                gthN = 2.0 * HD(H_QTHN) * et;
+            }
         }
-        gthN = P::from_lane(gthN, N - 1);
+        if (!VO) gthN = P::from_lane(gthN, N - 1);
     }
     // psi = f + c/2 dist^2_C(F1 + y/max(c,1)) + c/2 ||F2||^2 in ONE wave reduction of per-lane partials
     // (item lanes: stage costs; vector lanes: per-step costs + box distance; lanes < Kd: their F2 entry)
@@ -1669,7 +1704,8 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
 // ------------------------------------------------------------------------------------------------
 // test-hook kernel: one evaluation per problem through eval_point
 // ------------------------------------------------------------------------------------------------
-template <int NT, bool SC, class P, bool AXIS = false, bool LIN = false>
+// VO: psi alone through the value-only form of eval_point (mpcgpu_psi_value_batch); the other outputs are not written
+template <int NT, bool SC, class P, bool AXIS = false, bool LIN = false, bool VO = false>
 __global__ __launch_bounds__(WAVE) void cost_grad_kernel(KParams kp, BatchPtrs io, const double* __restrict__ u,
                                                          const double* __restrict__ xi, double* psi, double* f,
                                                          double* grad, double* F1, double* F2, int B) {
@@ -1689,6 +1725,11 @@ __global__ __launch_bounds__(WAVE) void cost_grad_kernel(KParams kp, BatchPtrs i
 #ifdef MPC_PROFILE
     Prof prof; prof.start();
 #endif
+    if (VO) {
+        eval_point<NT, SC, P, AXIS, LIN, 3, true>(kp, cx, v, w, c, 1.0 / fmax(c, 1.0), ya, yb, false, false, o PROF_PASS);
+        if (lane == 0 && psi) psi[b] = o.psi;
+        return;
+    }
     eval_point<NT, SC, P, AXIS, LIN>(kp, cx, v, w, c, 1.0 / fmax(c, 1.0), ya, yb, true, true, o PROF_PASS);
     if (lane == 0) {
         if (psi) psi[b] = o.psi;
@@ -2658,7 +2699,7 @@ __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& i
                     PROF_MARK(10 + ST_LIP);
                     PROF_COUNT(16 + ST_LIP);
                     ++n_eval;
-                    eval_point<NT, SC, P, AXIS, LIN, MINW>(kp, cx, hv, hw, c, icm, ya, yb, false, false, o PROF_PASS);
+                    eval_point<NT, SC, P, AXIS, LIN, MINW, MPC_VALUE_ONLY != 0>(kp, cx, hv, hw, c, icm, ya, yb, false, false, o PROF_PASS);
                     const double cost_half = o.psi;
                     if (panoc_lip_test_fails(cx, cost_half, cost, ip, ig, nfpr) && lip_it < MAX_LIP_IT && Lip < KC(K_MAX_LIP)) {
                         lb.flush();  // invalidate the L-BFGS buffer

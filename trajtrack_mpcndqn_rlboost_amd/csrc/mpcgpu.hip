@@ -1016,8 +1016,9 @@ int32_t mpcgpu_solve_batch(void* handle, int32_t B, const double* p, const doubl
     return 0;
 }
 
-int32_t mpcgpu_cost_grad_batch(void* handle, int32_t B, const double* u, const double* xi, const double* p,
-                               double* psi, double* f, double* grad, double* F1, double* F2) {
+// one evaluation per problem through the test-hook kernel; vo: its value-only instantiation, which writes psi alone
+static int32_t cost_grad_impl(void* handle, int32_t B, const double* u, const double* xi, const double* p,
+                              double* psi, double* f, double* grad, double* F1, double* F2, bool vo) {
     Handle* h = (Handle*)handle;
     if (!h) return -1;
     if (B < 0) return fail(h, -1, "B=%d is negative", B);
@@ -1047,7 +1048,7 @@ int32_t mpcgpu_cost_grad_batch(void* handle, int32_t B, const double* u, const d
     const size_t lds_cg = h->kp.l_total * sizeof(double);
 #define LAUNCH_CGA(NT, SC, PP, GRID, LDSB, AX)                                                                      \
     do {                                                                                                             \
-        auto kern = cost_grad_kernel<NT, SC, PP, AX>;                                                                \
+        auto kern = vo ? cost_grad_kernel<NT, SC, PP, AX, false, true> : cost_grad_kernel<NT, SC, PP, AX>;           \
         if (int r_ = opt_in_lds(h, (const void*)kern, (LDSB))) return r_;                                            \
         hipLaunchKernelGGL(kern, dim3(GRID), dim3(WAVE), (LDSB), s, h->kp, io, (const double*)h->u.ptr,              \
                            (const double*)h->xi.ptr, (double*)h->psi.ptr, (double*)h->f.ptr, (double*)h->grad.ptr,   \
@@ -1067,7 +1068,7 @@ int32_t mpcgpu_cost_grad_batch(void* handle, int32_t B, const double* u, const d
             case 40:
 #if MPC_LINEAR40
                 if (lin_cg) {
-                    auto kern = cost_grad_kernel<40, true, Solo<40>, true, true>;
+                    auto kern = vo ? cost_grad_kernel<40, true, Solo<40>, true, true, true> : cost_grad_kernel<40, true, Solo<40>, true, true>;
                     if (int r_ = opt_in_lds(h, (const void*)kern, lds_cg)) return r_;
                     hipLaunchKernelGGL(kern, dim3(B), dim3(WAVE), lds_cg, s, h->kp, io, (const double*)h->u.ptr, (const double*)h->xi.ptr,
                                        (double*)h->psi.ptr, (double*)h->f.ptr, (double*)h->grad.ptr, (double*)h->F1.ptr, (double*)h->F2.ptr, B);
@@ -1096,6 +1097,16 @@ int32_t mpcgpu_cost_grad_batch(void* handle, int32_t B, const double* u, const d
     if (F2) HIP_OK(h, hipMemcpyAsync(F2, h->F2.ptr, Bz * nd * 8, hipMemcpyDeviceToHost, s));
     HIP_OK(h, hipStreamSynchronize(s));
     return 0;
+}
+
+int32_t mpcgpu_cost_grad_batch(void* handle, int32_t B, const double* u, const double* xi, const double* p,
+                               double* psi, double* f, double* grad, double* F1, double* F2) {
+    return cost_grad_impl(handle, B, u, xi, p, psi, f, grad, F1, F2, false);
+}
+
+int32_t mpcgpu_psi_value_batch(void* handle, int32_t B, const double* u, const double* xi, const double* p, double* psi) {
+    if (handle && B > 0 && !psi) return fail((Handle*)handle, -1, "psi must not be NULL");
+    return cost_grad_impl(handle, B, u, xi, p, psi, nullptr, nullptr, nullptr, nullptr, true);
 }
 
 int32_t mpcgpu_last_timing(void* handle, double* prep_ms, double* solve_ms) {

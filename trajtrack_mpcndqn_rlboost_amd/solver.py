@@ -63,7 +63,7 @@ class _CConfig(C.Structure):
 
 
 EXPORTS = ("mpcgpu_abi_version", "mpcgpu_create", "mpcgpu_destroy", "mpcgpu_last_error", "mpcgpu_num_params",
-           "mpcgpu_solve_batch", "mpcgpu_solve_batch_dev", "mpcgpu_cost_grad_batch", "mpcgpu_last_timing",
+           "mpcgpu_solve_batch", "mpcgpu_solve_batch_dev", "mpcgpu_cost_grad_batch", "mpcgpu_psi_value_batch", "mpcgpu_last_timing",
            "mpcgpu_last_eval_counts", "mpcgpu_last_shape", "mpcgpu_last_waves_per_simd", "mpcgpu_reserve_shape",
            "mpcgpu_set_option", "mpcgpu_last_problems_per_wavefront", "mpcgpu_last_ordered", "mpcgpu_last_tail_promotion", "mpcgpu_last_tail_timeouts", "mpcgpu_last_tail_timing", "mpcgpu_last_latency_kernel", "mpcgpu_reserve_batch", "mpcgpu_last_table_kind", "mpcgpu_tracker_window_dev",
            "mpcgpu_tracker_step_dev", "mpcgpu_rl_reference_dev", "mpcgpu_hint_switch_dev", "mpcgpu_debug_read_workspace",
@@ -98,7 +98,8 @@ _libs = {}
 
 
 def variant_path(name: str) -> str:
-    """Path of a test-only variant build (csrc/Makefile `variants`): 'trace', 'lbfgs_lds', 'twoloop', 'onesite', 'linear40'."""
+    """Path of a test-only variant build (csrc/Makefile `variants`): 'trace', 'lbfgs_lds', 'twoloop', 'onesite', 'linear40',
+    'step_r6', 'vo0' ..."""
     return os.path.join(_PKG, "variants", f"libmpcgpu_{name}.so")
 
 
@@ -136,6 +137,9 @@ def load_library(path: Optional[str] = None):
     L.mpcgpu_solve_batch_dev.restype = C.c_int32
     L.mpcgpu_cost_grad_batch.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp]
     L.mpcgpu_cost_grad_batch.restype = C.c_int32
+    if hasattr(L, "mpcgpu_psi_value_batch"):   # (absent only in an older build loaded for an A/B run)
+        L.mpcgpu_psi_value_batch.argtypes = [vp, C.c_int32, dp, dp, dp, dp]
+        L.mpcgpu_psi_value_batch.restype = C.c_int32
     L.mpcgpu_last_timing.argtypes = [vp, dp, dp]
     L.mpcgpu_last_timing.restype = C.c_int32
     L.mpcgpu_last_eval_counts.argtypes = [vp, C.c_int32, ip, ip, vp]
@@ -399,8 +403,7 @@ class BatchSolver:
                                         _ip(out.get("inner_it")), _ip(out.get("outer_it")), None, None, None, None)
         self._check(rc, "mpcgpu_solve_batch")
 
-    def cost_grad(self, u, p, c=None, y=None):
-        """Test hook: psi, f, grad psi, F1, F2 of every problem (GPU evaluation of the generated functions)."""
+    def _hook_inputs(self, u, p, c, y):
         p = np.ascontiguousarray(p, dtype=np.float64)
         u = np.ascontiguousarray(u, dtype=np.float64)
         if p.ndim == 1:
@@ -413,6 +416,19 @@ class BatchSolver:
             xi[:, 0] = c
         if y is not None:
             xi[:, 1:] = y
+        return B, u, p, xi
+
+    def psi_value(self, u, p, c=None, y=None):
+        """Test hook: psi of every problem through the value-only form of the evaluation (the Lipschitz test's code path)."""
+        B, u, p, xi = self._hook_inputs(u, p, c, y)
+        psi = np.empty(B)
+        rc = self._L.mpcgpu_psi_value_batch(self._h, B, _dp(u), _dp(xi), _dp(p), _dp(psi))
+        self._check(rc, "mpcgpu_psi_value_batch")
+        return psi
+
+    def cost_grad(self, u, p, c=None, y=None):
+        """Test hook: psi, f, grad psi, F1, F2 of every problem (GPU evaluation of the generated functions)."""
+        B, u, p, xi = self._hook_inputs(u, p, c, y)
         psi = np.empty(B); f = np.empty(B); grad = np.empty((B, self.n)); F1 = np.empty((B, self.n))
         F2 = np.empty((B, int(self.config.Ndynobs)))
         rc = self._L.mpcgpu_cost_grad_batch(self._h, B, _dp(u), _dp(xi), _dp(p), _dp(psi), _dp(f), _dp(grad),
