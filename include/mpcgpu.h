@@ -312,7 +312,7 @@ int32_t mpcgpu_last_tail_timeouts(void* handle, int32_t* timeouts, void* stream)
 typedef struct mpcgpu_tracker {
     int32_t B;                 /* robots */
     int32_t ref_cap;           /* rows of every robot's slice of `ref` */
-    int32_t action_steps;      /* inputs applied per tick (config action_steps) */
+    int32_t action_steps;      /* config action_steps (1..N): window [idx - a, idx + 5a); the tick takes ONE step under input u[a - 1] */
     int32_t _pad;
     double* states;            /* [B][3]  (x, y, theta), in/out */
     const double* goals;       /* [B][3]  final goals */

@@ -58,12 +58,12 @@ def test_polygon_distance_and_mitre_inflation():
     assert len(out) == 4 and np.isclose(np.min(out[:, 0]), -2.5, atol=1e-9)
 
 
-@pytest.mark.parametrize("args", [(10, 2, 10), (3.0, 1.0, 2), (1.5, 0.5, 0)])
-def test_batched_switcher_equals_the_scalar_one(args):
-    """BatchedHintSwitcher (array operations over robots) against one scalar HintSwitcher per robot -- which the
-    previous tests pin to the reference's class -- on random drives past random obstacle sets of different sizes."""
+def _drive_both_switchers(args, R, S, T=150):
+    """Random drives past random obstacle sets of different sizes: one scalar HintSwitcher per robot (handed R rows of the
+    original reference and S rows of the proposal) next to BatchedHintSwitcher.  Returns the number of consulted
+    robot-ticks on which the LONGER of the two trajectories enters an obstacle only beyond row min(R, S) - 1."""
     rng = np.random.default_rng(1)
-    B, R, T, O, V = 40, 20, 150, 5, 4
+    B, O, V = 40, 5, 4
     scal = [hybrid.HintSwitcher(*args) for _ in range(B)]
     bat = hybrid.BatchedHintSwitcher(B, *args)
     nst = rng.integers(0, 4, B)
@@ -71,14 +71,19 @@ def test_batched_switcher_equals_the_scalar_one(args):
     static = [[(base[:(3 if rng.random() < 0.3 else 4)] + [rng.uniform(2, 30), rng.uniform(0, 2)]).tolist()
                for _ in range(nst[b])] for b in range(B)]
     x = np.zeros(B)
-    seen_on = seen_off = toggles = 0
+    seen_on = seen_off = toggles = beyond = 0
     prev = np.zeros(B, dtype=bool)
+    common, longest = min(R, S), max(R, S)
     for t in range(T):
         x += rng.uniform(0.05, 0.4, B)
         pos = np.stack([x, 1.0 + rng.normal(0, 1.0, B)], axis=1)
-        orig = np.stack([pos[:, None, 0] + 0.24 * np.arange(1, R + 1)[None], np.repeat(rng.uniform(0, 3, B)[:, None], R, 1),
-                         np.zeros((B, R))], axis=2)
+        rows = np.stack([pos[:, None, 0] + 0.24 * np.arange(1, longest + 1)[None], np.repeat(rng.uniform(0, 3, B)[:, None], longest, 1),
+                         np.zeros((B, longest))], axis=2)
         dyn = np.stack([x[:, None] + rng.uniform(-4, 8, (B, 2)), rng.uniform(-1, 5, (B, 2))], axis=2)
+        if R != S:           # a part of the fleet: a disc that only rows beyond the common ones of the longer trajectory enter
+            far = rng.random(B) < 0.3
+            dyn[far, 0] = np.stack([x[far] + 0.24 * (common + 10), rows[far, 0, 1]], axis=1)      # +-0.8: rows common + 7 .. common + 13
+        orig, prop = rows[:, :R], rows[:, :S]
         polygons, valid = np.zeros((B, O, V, 2)), np.zeros((B, O), dtype=bool)
         live = rng.random(B) < 0.9
         expect = []
@@ -88,13 +93,131 @@ def test_batched_switcher_equals_the_scalar_one(args):
                 polygons[b, :nst[b]] = hybrid.pad_polygons(static[b], V)
             valid[b, :nst[b]] = True
             polygons[b, 3:5], valid[b, 3:5] = np.array(rects), True
-            expect.append(scal[b].switch(pos[b], orig[b].tolist(), orig[b].tolist(), static[b] + rects) if live[b]
+            expect.append(scal[b].switch(pos[b], orig[b].tolist(), prop[b].tolist(), static[b] + rects) if live[b]
                           else scal[b].switch_on)
-        got = bat.switch(pos, orig, polygons, valid, live)
+        got = bat.switch(pos, orig, polygons, valid, live) if R == S else bat.switch(pos, orig, polygons, valid, live, proposal_rows=S)
         assert np.array_equal(np.array(expect), got), t
         assert np.array_equal(np.array([s.detach_cnt for s in scal]), bat.detach_cnt), t
+        inside = (hybrid.points_in_polygons(rows[..., :2], polygons) & valid[:, None, :]).any(axis=2)      # [B, longest]
+        beyond += int((live & ~inside[:, :common].any(axis=1) & inside[:, common:].any(axis=1)).sum())
         seen_on += int(got.sum()); seen_off += int((~got).sum()); toggles += int((got != prev).sum()); prev = got
     assert seen_on > 100 and seen_off > 100 and toggles > 20
+    return beyond
+
+
+@pytest.mark.parametrize("args", [(10, 2, 10), (3.0, 1.0, 2), (1.5, 0.5, 0)])
+def test_batched_switcher_equals_the_scalar_one(args):
+    """BatchedHintSwitcher (array operations over robots) against one scalar HintSwitcher per robot -- which the
+    previous tests pin to the reference's class -- on random drives past random obstacle sets of different sizes."""
+    _drive_both_switchers(args, 20, 20)
+
+
+@pytest.mark.parametrize("args", [(10, 2, 10), (3.0, 1.0, 2)])
+@pytest.mark.parametrize("R,S", [(40, 20), (20, 40)])
+def test_batched_switcher_walks_the_rows_both_trajectories_have(R, S, args):
+    """The scalar class walks zip(original_traj, new_traj): with a 40-row reference and the 20-row proposal (N_hor = 40) rows 20..39
+    of the reference are never tested, and with 20 against 40 all 20 are.  A part of the fleet meets an obstacle only on
+    rows >= 20 of the longer trajectory: those rows must not switch anybody on."""
+    beyond = _drive_both_switchers(args, R, S, T=60)
+    assert beyond > 100, beyond                      # the case is not vacuous: such robot-ticks occurred
+
+
+def test_tracked_reference_takes_the_proposal_rows_it_has():
+    """What BatchedHybrid tracks when N_hor differs from the proposal's 20 rows, as hint_switch_kernel builds `chosen`: rows
+    < min(N, 20) of a switched robot are the proposal with the original heading column, every other row is the original."""
+    rng = np.random.default_rng(4)
+    B = 6
+    on = np.array([True, False, True, True, False, True])
+    for N, S in ((40, 20), (20, 20), (20, 40), (1, 20)):
+        original, rl_ref = rng.normal(size=(B, N, 3)), rng.normal(size=(B, S, 2))
+        keep = original.copy()
+        got = hybrid.tracked_reference(original, rl_ref, on)
+        rows = min(N, S)
+        assert got.shape == (B, N, 3) and np.array_equal(original, keep)
+        assert np.array_equal(got[~on], original[~on])
+        assert np.array_equal(got[on][:, :rows, :2], rl_ref[on][:, :rows]) and np.array_equal(got[on][:, :rows, 2], original[on][:, :rows, 2])
+        assert np.array_equal(got[on][:, rows:], original[on][:, rows:])
+        for b in np.nonzero(on)[0]:                   # the common rows are ref_traj_filter(decay = 1) of the reference's loop
+            merged = np.concatenate([rl_ref[b, :rows], original[b, :rows, 2:3]], axis=1)
+            assert np.array_equal(got[b, :rows], hybrid.ref_traj_filter(original[b, :rows], merged, decay=1))
+
+
+def test_batched_hybrid_tracks_forty_rows_with_the_twenty_row_proposal():
+    """BatchedHybrid.tick at N_hor = 40, mode 2, around a stub tracker (no solver): the references handed to the tracker have
+    40 rows; a robot whose first 20 reference rows run through a near obstacle tracks the proposal on rows 0..19 (original
+    heading) and its own reference on rows 20..39; a robot that meets the obstacle on rows >= 20 only keeps its reference."""
+    import torch
+    from conftest import make_cfg
+    cfg = make_cfg(40)
+    seen = {}
+
+    class StubTracker:
+        def __init__(self, B):
+            self.config, self.B = cfg, B
+            self.states, self.last_actions = np.zeros((B, 3)), np.zeros((B, 2))
+            self.active = np.ones(B, dtype=bool)
+            self.ref_trajs = ()
+
+        def initialization(self, i, init_state, goal_state, path, mode="work"):
+            self.states[i] = init_state
+
+        def update_static_constraints(self, i, polys):
+            pass
+
+        def local_refs(self):
+            k = np.arange(1, 41)[None, :]
+            return np.stack([self.states[:, :1] + 0.2 * k, self.states[:, 1:2] + 0.0 * k, 0.25 + 0.0 * k + self.states[:, 2:3]], axis=2)
+
+        def step(self, refs=None):
+            seen["refs"], seen["original"] = np.array(refs), self.local_refs()
+
+    class StubEnv:          # what tick() touches of BatchedRaysEnv in mode 2
+        time_step = 0.2
+
+        def __init__(self, B):
+            self.device = torch.device("cpu")
+            self.state = torch.zeros(B, 24, dtype=torch.float64)
+            self.flags = torch.zeros(B, 3, dtype=torch.bool)
+            self.terminated = torch.zeros(B, dtype=torch.bool)
+
+        def set_agent_state(self, st):
+            self.state[:, :5] = torch.from_numpy(st)
+
+        @property
+        def agent_state(self):
+            return self.state[:, :5]
+
+        def observe(self):
+            return dict(external=torch.zeros(len(self.state), 32), internal=torch.zeros(len(self.state), 14))
+
+    class StubNet:
+        def greedy_actions(self, obs):
+            return torch.full((obs.shape[0],), 4)
+
+    B = 3
+    run = hybrid.BatchedHybrid.__new__(hybrid.BatchedHybrid)
+    run._torch, run.config, run.mode, run.B = torch, cfg, 2, B
+    run.env, run.q_net, run.tracker = StubEnv(B), StubNet(), StubTracker(B)
+    run.tracker.states[:] = [[1.0, 1.0, 0.0], [1.0, 5.0, 0.0], [1.0, 9.0, 0.0]]
+    run.maps = [dict(obstacles=[])] * B
+    run._n_static, run._n_dynamic = np.ones(B, dtype=int), np.zeros(B, dtype=int)
+    # one box per robot on its line: rows 4..9 for robot 0, rows 24..29 for robot 1, none near robot 2's
+    boxes = [[(1.9, 0.5), (3.1, 0.5), (3.1, 1.5), (1.9, 1.5)], [(5.9, 4.5), (7.1, 4.5), (7.1, 5.5), (5.9, 5.5)],
+             [(1.9, 0.5), (3.1, 0.5), (3.1, 1.5), (1.9, 1.5)]]
+    run._polygons, run._poly_valid = np.array(boxes, dtype=float)[:, None], np.ones((B, 1), dtype=bool)
+    run.switcher = hybrid.BatchedHintSwitcher(B, 10, 2, 10)
+    run.obs = run.env.observe()
+    run.last_dyn = None
+    run.done, run.success, run.collided = (np.zeros(B, dtype=bool) for _ in range(3))
+    run.steps, run.switch_on, run.switch_ticks, run.t = np.zeros(B, dtype=int), np.zeros(B, dtype=bool), np.zeros(B, dtype=int), 0
+    out = run.tick()
+    assert out["switch_on"].tolist() == [True, False, False]
+    refs, original = seen["refs"], seen["original"]
+    assert refs.shape == (B, 40, 3)
+    want, _ = hybrid.rl_reference(np.concatenate([run.tracker.states, run.tracker.last_actions], axis=1), np.full(B, 4), cfg.ts, steps=20, ref_speed=1.0)
+    assert np.array_equal(refs[0, :20, :2], want[0]) and np.array_equal(refs[0, :20, 2], original[0, :20, 2])
+    assert np.array_equal(refs[0, 20:], original[0, 20:]) and np.array_equal(refs[1:], original[1:])
+    assert not np.array_equal(refs[0, :20, :2], original[0, :20, :2])
 
 
 def test_batched_geometry_helpers_match_the_scalar_ones():

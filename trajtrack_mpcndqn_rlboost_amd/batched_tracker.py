@@ -162,7 +162,7 @@ class BatchedTracker:
 
     def step(self, mode: str = "work", initial_guess: Optional[np.ndarray] = None, refs: Optional[np.ndarray] = None,
              groups: Optional[Sequence[Sequence[int]]] = None):
-        """Solve all robots, apply the first ``action_steps`` inputs.  Returns (actions [B, nu], pred_states
+        """Solve all robots, take the step of :meth:`_apply`.  Returns (actions [B, nu], pred_states
         [B, N, ns], cost [B]); robots that already reached their goal keep their state (action 0).
         ``refs`` [B, N, 3]: the reference each robot tracks this tick (``get_action(current_ref_traj)``,
         ``interface_mpc.py:82-88``); default: the local window of its global reference.
@@ -207,13 +207,14 @@ class BatchedTracker:
         return actions, self.pred_states.copy(), self.last_result.cost
 
     def _apply(self, idx: np.ndarray, solution: np.ndarray) -> np.ndarray:
-        """Post-solve part of ``run_step`` for the robots ``idx`` (``trajectory_generator.py:325-339``): advance by the
-        first ``action_steps`` inputs, roll the prediction out; returns their applied first actions."""
+        """Post-solve part of ``run_step`` for the robots ``idx`` (``trajectory_generator.py:325-339``): the taken state, the
+        prediction rolled out from it; returns their applied first actions.  The reference computes EVERY taken state from the
+        state before the tick (``state_next = motion_model(state, u[i])``, :326-328) and keeps the last one: with
+        ``action_steps = a`` the robot moves by ONE step under input ``u[a - 1]`` (``rollout_after_solve``; the same thing for
+        a = 1)."""
         cfg = self.config
         u = solution.reshape(len(idx), cfg.N_hor, cfg.nu)
-        state = self.states[idx].copy()
-        for s in range(cfg.action_steps):
-            state = unicycle_model(state, u[:, s], cfg.ts)
+        state = unicycle_model(self.states[idx], u[:, cfg.action_steps - 1], cfg.ts)
         pred = np.empty((len(idx), cfg.N_hor, cfg.ns))
         rolling = state
         for k in range(cfg.N_hor):                      # rolled from the taken state, re-applying u[0] (reference quirk)

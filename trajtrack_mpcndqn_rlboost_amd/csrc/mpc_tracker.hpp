@@ -7,7 +7,8 @@
 //                            the compact workspace record of the solve kernel: prep_problem (mpc_kernels.hpp) reads the same
 //                            parameter indices through a source that maps them onto the tracker's own arrays -- the record is
 //                            bitwise what prep_kernel makes of the assembled vector;
-//   tracker_apply_kernel     the post-solve part of run_step (:325-339): take action_steps inputs, roll the prediction out;
+//   tracker_apply_kernel     the post-solve part of run_step (:325-339): the taken state (one step under input action_steps - 1,
+//                            as the reference's loop leaves it), the prediction rolled out from it;
 //   rl_reference_kernel      the DQN's proposal: decoded acceleration pair + 20-step rollout with decaying turn rate
 //                            (src/pkg_dqn/environment/agent.py:86-145, src/main.py:193-202);
 //   hint_switch_kernel       HintSwitcher.switch (src/main_pre.py:27-52) for every robot + the reference it tracks this tick

@@ -72,9 +72,12 @@ __global__ __launch_bounds__(128) void tracker_apply_kernel(TrackerView t, int N
         return;
     }
     double x = t.states[3 * b], y = t.states[3 * b + 1], th = t.states[3 * b + 2];
-    for (int s = 0; s < t.action_steps; ++s) unicycle_rk4(x, y, th, ub[2 * s], ub[2 * s + 1], ts);
+    // taken state: the reference computes every one of the action_steps taken states from the state BEFORE the tick
+    // (state_next = motion_model(state, u[i]), :326-328) and keeps the last -- ONE step under the input u[action_steps - 1]
+    const double* ul = ub + 2 * (t.action_steps - 1);
+    unicycle_rk4(x, y, th, ul[0], ul[1], ts);
     t.states[3 * b] = x; t.states[3 * b + 1] = y; t.states[3 * b + 2] = th;
-    t.last_actions[2 * b] = ub[2 * (t.action_steps - 1)]; t.last_actions[2 * b + 1] = ub[2 * (t.action_steps - 1) + 1];
+    t.last_actions[2 * b] = ul[0]; t.last_actions[2 * b + 1] = ul[1];
     if (actions_out) { actions_out[2 * b] = ub[0]; actions_out[2 * b + 1] = ub[1]; }
     // prediction: rolled from the TAKEN state with the whole input sequence again (the reference re-applies u[0]: kept)
     double* pr = t.pred_states + (size_t)b * N * 3;

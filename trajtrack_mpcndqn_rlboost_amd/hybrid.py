@@ -141,6 +141,21 @@ def filter_weights(n_rows: int, decay: float = 1.0) -> np.ndarray:
     return w
 
 
+def tracked_reference(original: np.ndarray, rl_ref: np.ndarray, switch_on: np.ndarray) -> np.ndarray:
+    """The reference every robot tracks this tick ([B, N, 3]), as ``hint_switch_kernel`` builds it: for a robot whose
+    switch is on, rows < min(N, rows of ``rl_ref``) are the proposal ``rl_ref`` [B, S, 2] with the heading column of
+    ``original`` [B, N, 3] (``ref_traj_filter`` with decay 1 on the rows both have, ``merge_reference``); the
+    remaining rows, and every row of the other robots, are the original reference."""
+    original = np.asarray(original, dtype=float)
+    rows = min(original.shape[1], np.shape(rl_ref)[1])
+    head = original[:, :rows]
+    proposal = merge_reference(np.asarray(rl_ref, dtype=float)[:, :rows], head)
+    w = filter_weights(rows, 1.0)[None, :, None]              # ref_traj_filter(decay=1): the proposal as it is
+    chosen = original.copy()
+    chosen[:, :rows] = np.where(np.asarray(switch_on, dtype=bool)[:, None, None], (1.0 - w) * head + w * proposal, head)
+    return chosen
+
+
 def pad_polygons(polygons: Sequence[Sequence[Sequence[float]]], n_vertices: int) -> np.ndarray:
     """[O, n_vertices, 2]: every ring padded by repeating its last vertex (zero-length edges change neither the
     even-odd test nor the distance)."""
@@ -190,16 +205,19 @@ class BatchedHintSwitcher:
         self.switch_on = np.zeros(self.B, dtype=bool)
 
     def switch(self, positions: np.ndarray, original: np.ndarray, polygons: np.ndarray, valid: np.ndarray,
-               live: Optional[np.ndarray] = None) -> np.ndarray:
+               live: Optional[np.ndarray] = None, proposal_rows: Optional[int] = None) -> np.ndarray:
         """positions [B, 2]; original [B, R, >= 2] (rows of the original reference); polygons [B, O, V, 2] with
-        ``valid`` [B, O] marking real obstacles; ``live`` [B]: robots whose switcher is consulted this tick."""
-        contains = points_in_polygons(np.asarray(original)[..., :2], polygons)      # [B, R, O]
+        ``valid`` [B, O] marking real obstacles; ``live`` [B]: robots whose switcher is consulted this tick;
+        ``proposal_rows``: rows of the proposal (default R).  The scalar class walks ``zip(original_traj, new_traj)``:
+        only the first ``min(R, proposal_rows)`` rows of the original reference are tested."""
+        rows = np.shape(original)[1] if proposal_rows is None else min(np.shape(original)[1], int(proposal_rows))
+        contains = points_in_polygons(np.asarray(original)[:, :rows, :2], polygons)  # [B, rows, O]
         dist = polygon_distances(np.asarray(positions, dtype=float), polygons)      # [B, O]
         on, cnt = self.switch_on, self.detach_cnt
         returned = np.zeros(self.B, dtype=bool) if live is None else ~np.asarray(live, dtype=bool)
         counted = np.zeros(self.B, dtype=bool)
         near, far = dist < self.switch_distance, dist > self.detach_distance
-        for r in range(contains.shape[1]):
+        for r in range(rows):
             for o in range(contains.shape[2]):
                 act = valid[:, o] & ~returned
                 c = contains[:, r, o]
@@ -334,9 +352,6 @@ class BatchedHybrid:
                 self._mark("environment kernel")
                 rl_ref, _ = rl_reference(env.agent_state.cpu().numpy(), actions, cfg.ts, steps=20, ref_speed=1.0)
                 original = trk.local_refs()
-                proposal = merge_reference(rl_ref[:, :cfg.N_hor], original)
-                w = filter_weights(cfg.N_hor, 1.0)[None, :, None]      # ref_traj_filter(decay=1): the proposal as it is
-                filtered = (1.0 - w) * original + w * proposal
                 if kmax:                                             # circle_to_rect of every disc (main.py:129)
                     r = DYN_OBS_SIZE
                     corners = np.array([[-r, -r], [r, -r], [r, r], [-r, r]])
@@ -344,10 +359,11 @@ class BatchedHybrid:
                     rects = dyn_now[:, :, None, :] + corners[None, None]
                     self._polygons[:, s0:s0 + kmax, :4] = rects
                     self._polygons[:, s0:s0 + kmax, 4:] = rects[:, :, 3:4]
-                on = self.switcher.switch(trk.states[:, :2], original, self._polygons, self._poly_valid, live)
+                on = self.switcher.switch(trk.states[:, :2], original, self._polygons, self._poly_valid, live,
+                                          proposal_rows=rl_ref.shape[1])
                 self.switch_on = on & live
                 self.switch_ticks += self.switch_on
-                chosen = np.where(self.switch_on[:, None, None], filtered, original)
+                chosen = tracked_reference(original, rl_ref, self.switch_on)   # N_hor rows: the proposal has 20
                 self._mark("RL reference + switch (host)")
             if kmax:
                 trk.set_dynamic_constraints(preds)
