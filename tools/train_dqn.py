@@ -34,6 +34,8 @@ import torch.distributed as dist
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 rl_env = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.rl_env")
+map_stream = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.map_stream")
+path_plan = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.path_plan")
 dqn_train = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.dqn_train")
 
 
@@ -47,6 +49,15 @@ def scene(rng):
                 [(7.2, 2.8), (7.2, 4.2), (8.8, 4.2), (8.8, 2.8)]],
         dynamic=[dict(p1=(10.0, 1.0), p2=(10.0, 9.0), freq=0.2, rx=0.8, ry=0.8, angle=0.0, corners=20)],
         start=[0.6, y0, th, 0.0, 0.0], goal=[15.4, 3.5], path=[(0.6, y0), (6.4, 5.4), (9.6, 5.4), (15.4, 3.5)])
+
+
+def fresh_start_maps(n: int, device: int):
+    """The maps the environments of --fresh-maps start on: a handful of host-built generate_map_dynamic maps, repeated (every row
+    moves to a map of its own at its first episode end)."""
+    specs = [map_stream.spec_of(2 ** 40, b) for b in range(16)]
+    paths, status = path_plan.plan_reference_paths(specs, device=device)
+    maps = [rl_env.make_map(path=p, **s) for s, p, st in zip(specs, paths, status) if st == 0][:4]
+    return [maps[i % len(maps)] for i in range(n)]
 
 
 def self_launch(gpus: int) -> int:
@@ -76,6 +87,9 @@ def main():
     ap.add_argument("--save", default=None, help="directory for best_model.pt / final_model.pt / checkpoint.pt")
     ap.add_argument("--resume", default=None, help="checkpoint.pt of an earlier run with the same arguments")
     ap.add_argument("--checkpoint-every", type=int, default=0, help="environment steps between checkpoints (0: only at the end)")
+    ap.add_argument("--fresh-maps", action="store_true",
+                    help="a new random map per episode, drawn and planned on the device (generate_map_dynamic; stream seed + rank)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the map stream of --fresh-maps")
     args = ap.parse_args()
     if os.environ.get("WORLD_SIZE") is None and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
@@ -88,7 +102,12 @@ def main():
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local))
     rng = np.random.default_rng(100 + rank)
     torch.manual_seed(0)
-    env = rl_env.BatchedRaysEnv([scene(rng) for _ in range(args.envs)], device=local, max_episode_steps=400)
+    if args.fresh_maps:
+        env = rl_env.BatchedRaysEnv(fresh_start_maps(args.envs, local), device=local, max_episode_steps=400,
+                                    capacity=map_stream.DYNAMIC_CAPACITY)
+        env.enable_fresh_maps(seed=args.seed + rank)
+    else:
+        env = rl_env.BatchedRaysEnv([scene(rng) for _ in range(args.envs)], device=local, max_episode_steps=400)
     trainer = dqn_train.DqnTrainer(device=f"cuda:{local}", double_q=args.double_q, lr=1e-3)
     learner = dqn_train.DqnLearner(env, trainer, buffer_size=2_000_000, learning_starts=4 * args.envs,
                                    batch_size=args.batch_size, train_freq=4, gradient_steps=args.gradient_steps,

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <string>
 
+#include "../../include/mpcgpu_map.h"
 #include "envgpu_internal.hpp"
 
 namespace envgpu {
@@ -100,8 +101,11 @@ __constant__ double DIRS[16] = {0.0, 0.38268343236508978178, 0.70710678118654757
                                 0.0, -0.38268343236508978178, -0.70710678118654757274, -0.92387953251128673848,
                                 -1.0, -0.92387953251128673848, -0.70710678118654757274, -0.38268343236508978178};
 
+// FRESH (include/mpcgpu_map.h): rec_all is a [2][B][rec] table, row b steps on table which[b], and an episode that ends while
+// spare_ready[b] is set starts its next episode on the other table.  Everything FRESH adds sits under `if constexpr`.
+template <bool FRESH>
 __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double* __restrict__ rec_all, double* state_all,
-                                                        const int32_t* __restrict__ action, EnvOut out, int B) {
+                                                        const int32_t* __restrict__ action, EnvOut out, int B, EnvFresh fr) {
     float* const obs_int = out.obs_int;
     float* const obs_ext = out.obs_ext;
     double* const reward = out.reward;
@@ -112,10 +116,11 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
     if (b >= B) return;
     const int lane = threadIdx.x;
     const double* rec = rec_all + (size_t)b * k.rec;
+    if constexpr (FRESH) rec = rec_all + ((size_t)fr.which[b] * B + b) * k.rec;
     double* st = state_all + (size_t)b * SDIM;
     const mpcgpu_env_params& P = k.p;
-    const int n_path = (int)rec[0], n_obst = (int)rec[1], n_edge = (int)rec[2];
-    const double gx = rec[3], gy = rec[4];
+    int n_path = (int)rec[0], n_obst = (int)rec[1], n_edge = (int)rec[2];   // (not const: FRESH re-reads them with the record)
+    double gx = rec[3], gy = rec[4];
     double x = st[0], y = st[1], th = st[2], v = st[3], w = st[4], clock = st[5];
     double last_prog = st[6], steps = st[25];
     int flags = (int)st[7];
@@ -421,6 +426,19 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
     if (out.term_ext && lane < MPCGPU_ENV_EXTERNAL_OBS)
         out.term_ext[(size_t)b * MPCGPU_ENV_EXTERNAL_OBS + lane] = obs_ext[(size_t)b * MPCGPU_ENV_EXTERNAL_OBS + lane];
     __syncthreads();
+    if constexpr (FRESH) {
+        // every lane reads the row's two words before lane 0 rewrites them; the workgroup owns the row, so no atomics
+        const int cur = fr.which[b], ready = fr.spare_ready[b];
+        __syncthreads();
+        if (ready) {
+            rec = rec_all + ((size_t)(cur ^ 1) * B + b) * k.rec;
+            n_path = (int)rec[0]; n_obst = (int)rec[1]; n_edge = (int)rec[2];
+            gx = rec[3]; gy = rec[4];
+            if (lane == 0) { fr.which[b] = cur ^ 1; fr.spare_ready[b] = 0; fr.loaded[b] += 1; }
+        } else if (lane == 0) {
+            fr.stale[b] += 1;
+        }
+    }
     x = rec[5]; y = rec[6]; th = rec[7]; v = rec[8]; w = rec[9];
     clock = 0.0; flags = 0; steps = 0.0; last_prog = 0.0; act = false;
     sincos(th, &sth0, &cth0);
@@ -437,7 +455,7 @@ int fail(const char* what, hipError_t e) {
 }
 
 int launch_step(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records, double* state,
-                const int32_t* action, EnvOut out, bool need_ext, void* stream) {
+                const int32_t* action, EnvOut out, bool need_ext, void* stream, const EnvFresh* fresh) {
     EnvK k;
     if (!params || !layout(*params, k)) return fail("invalid mpcgpu_env_params (P 2..64, M 0..31, K 1..4, E >= 1)");
     if (params->num_segments != NSEG || params->corner_samples != NCORNER)
@@ -446,7 +464,12 @@ int launch_step(int32_t device, const mpcgpu_env_params* params, int32_t B, cons
     if (B == 0) return 0;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return fail("hipSetDevice", e);
-    hipLaunchKernelGGL(env_step_kernel, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state, action, out, (int)B);
+    if (fresh)
+        hipLaunchKernelGGL(env_step_kernel<true>, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state, action, out,
+                           (int)B, *fresh);
+    else
+        hipLaunchKernelGGL(env_step_kernel<false>, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state, action, out,
+                           (int)B, EnvFresh{});
     e = hipGetLastError();
     if (e != hipSuccess) return fail("env_step_kernel launch", e);
     return 0;
@@ -481,5 +504,22 @@ int32_t mpcgpu_env_step_autoreset_dev(int32_t device, const mpcgpu_env_params* p
 }
 
 const char* mpcgpu_env_last_error(void) { return envgpu::g_err.c_str(); }
+
+// include/mpcgpu_map.h
+int32_t mpcgpu_env_step_fresh_dev(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records2,
+                                  int32_t* which, int32_t* spare_ready, int32_t* loaded, int32_t* stale, double* state,
+                                  const int32_t* action, float* obs_internal, float* obs_external, double* reward,
+                                  uint8_t* terminated, uint8_t* truncated, float* terminal_obs_internal,
+                                  float* terminal_obs_external, int32_t max_episode_steps, void* stream) {
+    if (!which || !spare_ready || !loaded || !stale) return envgpu::fail("null pointer (which / spare_ready / loaded / stale)");
+    if (max_episode_steps < 0) return envgpu::fail("max_episode_steps must not be negative");
+    if (max_episode_steps > 0 && !action) return envgpu::fail("auto-reset needs actions (max_episode_steps = 0 observes)");
+    if (max_episode_steps > 0 && !truncated) return envgpu::fail("null pointer (truncated)");
+    envgpu::EnvOut out{obs_internal, obs_external, reward, terminated, max_episode_steps > 0 ? truncated : nullptr,
+                       max_episode_steps > 0 ? terminal_obs_internal : nullptr,
+                       max_episode_steps > 0 ? terminal_obs_external : nullptr, max_episode_steps, nullptr};
+    const envgpu::EnvFresh fresh{which, spare_ready, loaded, stale};
+    return envgpu::launch_step(device, params, B, records2, state, action, out, true, stream, &fresh);
+}
 
 }  // extern "C"

@@ -24,6 +24,11 @@ struct EnvOut {
     double* pre_reset;
 };
 
+// the fresh-map step (include/mpcgpu_map.h): per-row table selector, spare flag and the two counters; unused (null) otherwise
+struct EnvFresh {
+    int32_t* which; int32_t* spare_ready; int32_t* loaded; int32_t* stale;
+};
+
 // per-environment image state (mpcgpu_env_img_state_doubles): [0] observations since the last reset, [1..6] obstacle
 // clock of each of the last 6 observations (ring, slot (k - 1) % 6 holds observation k), [7] reserved,
 // [8..11] x, y, theta, clock of the last step before an in-kernel reset, [12] 1 when that reset happened, [13..15] reserved
@@ -33,8 +38,9 @@ constexpr int IMG_PRE = 8;
 
 bool layout(const mpcgpu_env_params& p, EnvK& k);
 int fail(const char* what, hipError_t e = hipSuccess);
-// validates params and pointers (obs_ext may be NULL when need_ext is false) and enqueues env_step_kernel
+// validates params and pointers (obs_ext may be NULL when need_ext is false) and enqueues env_step_kernel<false>, or
+// env_step_kernel<true> on a [2][B][rec] table when `fresh` is given
 int launch_step(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records, double* state,
-                const int32_t* action, EnvOut out, bool need_ext, void* stream);
+                const int32_t* action, EnvOut out, bool need_ext, void* stream, const EnvFresh* fresh = nullptr);
 
 }  // namespace envgpu

@@ -94,9 +94,10 @@ class PathPlanner:
         self.device_index = device
         self.n_node_max = int(n_node_max)
 
-    def plan_dev(self, records, start_goal, n_vert_max: int, n_ring_max: int):
+    def plan_dev(self, records, start_goal, n_vert_max: int, n_ring_max: int, out=None):
         """Device tensors in, device tensors out, nothing synchronises: ``records`` [B, R] and ``start_goal`` [B, 4]
-        float64 -> (status int32 [B], n_nodes int32 [B], nodes float64 [B, 64, 2], length float64 [B])."""
+        float64 -> (status int32 [B], n_nodes int32 [B], nodes float64 [B, 64, 2], length float64 [B]).  ``out``: the
+        four tensors of an earlier call, written again instead of allocating new ones."""
         torch = self._torch
         params = _CPlanParams(int(n_vert_max), int(n_ring_max), self.n_node_max, 0)
         R = self._lib.mpcgpu_plan_record_doubles(C.byref(params))
@@ -106,10 +107,13 @@ class PathPlanner:
         if records.shape != (B, R) or start_goal.shape != (B, 4) or records.dtype != torch.float64 or \
                 start_goal.dtype != torch.float64 or not records.is_contiguous() or not start_goal.is_contiguous():
             raise ValueError(f"records must be contiguous float64 [B, {R}] and start_goal float64 [B, 4]")
-        status = torch.empty(B, dtype=torch.int32, device=self.device)
-        n_nodes = torch.empty(B, dtype=torch.int32, device=self.device)
-        nodes = torch.empty(B, MAX_PATH_NODES, 2, dtype=torch.float64, device=self.device)
-        length = torch.empty(B, dtype=torch.float64, device=self.device)
+        if out is not None:
+            status, n_nodes, nodes, length = out
+        else:
+            status = torch.empty(B, dtype=torch.int32, device=self.device)
+            n_nodes = torch.empty(B, dtype=torch.int32, device=self.device)
+            nodes = torch.empty(B, MAX_PATH_NODES, 2, dtype=torch.float64, device=self.device)
+            length = torch.empty(B, dtype=torch.float64, device=self.device)
         rc = self._lib.mpcgpu_plan_paths_dev(self.device_index, C.byref(params), B, records.data_ptr(), start_goal.data_ptr(),
                                              status.data_ptr(), n_nodes.data_ptr(), nodes.data_ptr(), length.data_ptr(),
                                              torch.cuda.current_stream(self.device).cuda_stream)

@@ -229,7 +229,9 @@ class BatchedRaysEnv:
     def __init__(self, maps: Sequence[Dict], device: int = 0, time_step: float = 0.2, max_episode_steps: int = 1000,
                  sample_offset: float = 0.0, collision_factor: float = 4.0, reach_goal_factor: float = 3.0,
                  cross_track_factor: float = 0.05, reference_speed: float = ROBOT["speed_max"] * 0.8,
-                 path_progress_factor: float = 2.0):
+                 path_progress_factor: float = 2.0, capacity: Optional[Dict] = None):
+        """``capacity`` (``n_path_max``, ``n_obst_max``, ``n_kf_max``, ``n_edge_max``) sizes the record table for maps that
+        come later (:meth:`replace_maps`, :meth:`load_spares`) instead of for ``maps`` alone; ``maps`` must fit it."""
         import torch
         if not torch.cuda.is_available():
             raise MpcGpuError("BatchedRaysEnv needs a HIP device: the environment step is a GPU kernel, there is no CPU path")
@@ -238,7 +240,7 @@ class BatchedRaysEnv:
         self.device = torch.device("cuda", device)
         self.device_index = device
         self.B = len(maps)
-        rec, maxima = pack_records(maps)
+        rec, maxima = pack_records(maps, limits=capacity)
         self.params = _CParams(num_segments=8, corner_samples=3, time_step=time_step, sample_offset=sample_offset,
                                collision_factor=collision_factor, reach_goal_factor=reach_goal_factor,
                                cross_track_factor=cross_track_factor, excessive_speed_factor=2.0 * path_progress_factor,
@@ -261,12 +263,114 @@ class BatchedRaysEnv:
         self.term_external = torch.zeros_like(self.obs_external)
         self.max_episode_steps = max_episode_steps
         self.time_step = time_step
+        self.records2 = None     # [2, B, R] once enable_spares() ran; self.records is then its table 0
+
+    # ---- a spare record per row: map turnover inside the auto-reset step (include/mpcgpu_map.h) --------------------
+    def _limits(self) -> Dict:
+        return {k: int(getattr(self.params, k)) for k in ("n_path_max", "n_obst_max", "n_kf_max", "n_edge_max")}
+
+    def enable_spares(self) -> None:
+        """Give every row a second record.  From now on ``step(actions, auto_reset=True)`` launches the fresh-map variant
+        of the step kernel: a row whose episode ends while its spare is ready (:meth:`load_spares`) starts the next
+        episode on the spare inside that launch -- counted in ``loaded`` -- and otherwise resets on the map it has --
+        counted in ``stale``.  ``which`` [B] says which of the two tables a row is on; ``reset``, ``observe``,
+        ``replace_maps`` and the step without auto-reset act on that table.  Device memory: a second table of B * R
+        doubles (R = ``records.shape[1]``) and four int32 vectors of B."""
+        if self.records2 is not None:
+            return
+        from . import map_stream
+        map_stream._bind(self._lib)
+        torch = self._torch
+        self.records2 = torch.stack([self.records, self.records]).contiguous()
+        self.records = self.records2[0]
+        for name in ("which", "spare_ready", "loaded", "stale"):
+            setattr(self, name, torch.zeros(self.B, dtype=torch.int32, device=self.device))
+        self._rows = torch.arange(self.B, device=self.device)
+
+    def enable_fresh_maps(self, seed: int = 0, refill_every: int = 16) -> None:
+        """A new random map per episode, drawn, planned and packed on the device (``map_stream``, ``csrc/mapgpu.hip``):
+        :meth:`enable_spares`, then every ``refill_every``-th ``step(actions, auto_reset=True)`` enqueues a refill behind the
+        step -- for the rows whose spare is missing: draw map ``b + B * attempt[b]`` of stream ``seed``
+        (``map_stream.spec_of``), inflate its outlines, plan its reference path (``csrc/plangpu.hip``) and pack the record
+        into the spare slot.  A row whose draw has no path, or does not fit, draws again at the next refill.  Nothing
+        synchronises with the host.  The default ``refill_every`` is the largest of 1, 4, 8, 16, 32 without a stale reset
+        in 2000 steps of random actions at B = 4096 (``profiles/map_stream_bench.txt``).  ``refill_status`` [B] keeps ``map_stream.STATUS`` of the last refill.  Raises
+        ``ValueError``, before anything is allocated, if the record table is smaller than ``map_stream.DYNAMIC_CAPACITY``
+        (build the environment with ``capacity=map_stream.DYNAMIC_CAPACITY``).  Extra device memory: the second record
+        table (B * R doubles), the spec (288), ring (396) and path (130) tables of B rows, and six int32 vectors."""
+        from . import map_stream, path_plan
+        short = [k for k, v in map_stream.DYNAMIC_CAPACITY.items() if getattr(self.params, k) < v]
+        if short:
+            raise ValueError("the record table is smaller than map_stream.DYNAMIC_CAPACITY in " + ", ".join(short))
+        if int(refill_every) < 1:
+            raise ValueError("refill_every must be at least 1")
+        self.enable_spares()
+        torch = self._torch
+        self.fresh_seed, self.refill_every = int(seed), int(refill_every)
+        self.attempt = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self.refill_status = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
+        self._spec = torch.zeros(self.B, map_stream.SPEC_DOUBLES, dtype=torch.float64, device=self.device)
+        self._planner = path_plan.PathPlanner(self.device_index)
+        self._calls = 0
+        self._rings = self._plan = None     # ring records, start / goal and planner output: allocated by the first refill
+        self.refill()
+
+    def refill(self) -> None:
+        """Enqueue one refill of the missing spares on the current stream (draw, rings, plan, record: four launches)."""
+        from . import map_stream
+        map_stream.draw_specs_dev(self._spec, self.spare_ready, self.attempt, self.fresh_seed, self.device_index)
+        self._rings = rings, start_goal = map_stream.rings_dev(self._spec, self.spare_ready, self.device_index, out=self._rings)
+        self._plan = self._planner.plan_dev(rings, start_goal, map_stream.VERT_MAX, map_stream.RING_MAX, out=self._plan)
+        status, n_nodes, nodes, _ = self._plan
+        map_stream.records_dev(self.params, self._spec, status, n_nodes, nodes, self.records2, self.which, self.spare_ready,
+                               self.refill_status, self.device_index)
+
+    def load_spares(self, rows, maps: Sequence[Dict]) -> None:
+        """Pack ``maps`` (:func:`make_map`) into the spare records of ``rows`` and mark them ready; a spare that was ready
+        is replaced.  Raises ``ValueError``, before anything is written, if a map does not fit the table.  Enqueued on
+        the current stream, like the step that will read them."""
+        torch = self._torch
+        if self.records2 is None:
+            raise MpcGpuError("load_spares needs enable_spares() first")
+        rows = [int(r) for r in rows]
+        if len(rows) != len(maps) or len(set(rows)) != len(rows) or any(r < 0 or r >= self.B for r in rows):
+            raise ValueError(f"load_spares needs one map per row, rows distinct and in [0, {self.B})")
+        if not rows:
+            return
+        rec, _ = pack_records(maps, limits=self._limits())
+        idx = torch.as_tensor(rows, dtype=torch.int64, device=self.device)
+        self.records2[1 - self.which[idx].long(), idx] = torch.from_numpy(rec).to(self.device)
+        self.spare_ready[idx] = 1
+
+    def current_records(self):
+        """[B, R] copy of the record every row is on."""
+        if self.records2 is None:
+            return self.records.clone()
+        return self.records2[self.which.long(), self._rows]
+
+    def _fresh_launch(self, actions, max_steps: int) -> None:
+        torch = self._torch
+        aptr = None
+        if actions is not None:
+            actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
+            if actions.shape != (self.B,):
+                raise ValueError(f"actions must have shape ({self.B},)")
+            aptr = actions.data_ptr()
+        rc = self._lib.mpcgpu_env_step_fresh_dev(
+            self.device_index, C.byref(self.params), self.B, self.records2.data_ptr(), self.which.data_ptr(),
+            self.spare_ready.data_ptr(), self.loaded.data_ptr(), self.stale.data_ptr(), self.state.data_ptr(), aptr,
+            self.obs_internal.data_ptr(), self.obs_external.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
+            self.truncated.data_ptr(), self.term_internal.data_ptr(), self.term_external.data_ptr(), int(max_steps),
+            torch.cuda.current_stream(self.device).cuda_stream)
+        if rc != 0:
+            raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
 
     def replace_maps(self, rows, maps: Sequence[Dict]) -> None:
         """Give environments ``rows`` the new ``maps`` (:func:`make_map`, e.g. with a path of ``path_plan``): their rows
         of the device record table are re-packed in place, no other row is touched.  Raises ``ValueError``, before
         anything is written, if a map exceeds the table's ``n_path_max``, ``n_obst_max``, ``n_kf_max`` or
-        ``n_edge_max``.  The rows keep their state until a following ``reset(mask)`` starts them on the new maps."""
+        ``n_edge_max``.  The rows keep their state until a following ``reset(mask)`` starts them on the new maps.  After
+        :meth:`enable_spares` it is the record a row is ON that is replaced; its spare is left alone."""
         torch = self._torch
         rows = [int(r) for r in rows]
         if len(rows) != len(maps) or len(set(rows)) != len(rows) or any(r < 0 or r >= self.B for r in rows):
@@ -278,12 +382,17 @@ class BatchedRaysEnv:
         assert rec.shape[1] == self.records.shape[1]
         idx = torch.as_tensor(rows, dtype=torch.int64, device=self.device)
         start = np.stack([np.asarray(m["start"], dtype=np.float64) for m in maps])
+        if self.records2 is not None:
+            self.records2[self.which[idx].long(), idx] = torch.from_numpy(rec).to(self.device)
+            return                                  # the start state is read from the current record
         self.records[idx] = torch.from_numpy(rec).to(self.device)
         self._start[idx] = torch.from_numpy(start).to(self.device)
 
     # ---- kernel launch ---------------------------------------------------------------------------------------------
     def _launch(self, actions) -> None:
         torch = self._torch
+        if self.records2 is not None:
+            return self._fresh_launch(actions, 0)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         aptr = None
         if actions is not None:
@@ -311,7 +420,7 @@ class BatchedRaysEnv:
         mask = torch.as_tensor(mask, device=self.device).bool()
         keep = self.state[:, 8:24].clone()
         fresh = torch.zeros_like(self.state)
-        fresh[:, :5] = self._start
+        fresh[:, :5] = self._start if self.records2 is None else self.records2[self.which.long(), self._rows, 5:10]
         fresh[:, 8:24] = keep
         self.state = torch.where(mask[:, None], fresh, self.state)
         # update_status(reset=True) + get_observation for the reset rows only: the launch observes every environment, so the
@@ -331,12 +440,29 @@ class BatchedRaysEnv:
     def state_dict(self) -> Dict:
         """Everything a continuation needs: robot / clock state (incl. the one-step observation memory kept in it) and the
         observation, reward and flags of the last launch."""
-        return dict(state=self.state.clone(), obs_internal=self.obs_internal.clone(), obs_external=self.obs_external.clone(),
-                    reward=self.reward.clone(), terminated=self.terminated.clone(), truncated=self.truncated.clone())
+        d = dict(state=self.state.clone(), obs_internal=self.obs_internal.clone(), obs_external=self.obs_external.clone(),
+                 reward=self.reward.clone(), terminated=self.terminated.clone(), truncated=self.truncated.clone())
+        if self.records2 is not None:
+            # maps change while the environment runs: both record tables (2 * B * R doubles, R = records.shape[1]; 16 * B * R
+            # bytes) and the per-row vectors belong to the state
+            d.update({k: getattr(self, k).clone() for k in self._FRESH_KEYS if getattr(self, k, None) is not None})
+            if getattr(self, "refill_every", 0):
+                d["refill_calls"] = self._calls
+        return d
+
+    _FRESH_KEYS = ("records2", "which", "spare_ready", "loaded", "stale", "attempt")
 
     def load_state_dict(self, d: Dict) -> None:
+        if ("records2" in d) != (self.records2 is not None):
+            raise ValueError("state_dict and environment differ in enable_spares()")
         for k in ("state", "obs_internal", "obs_external", "reward", "terminated", "truncated"):
             getattr(self, k).copy_(d[k].to(self.device))
+        if self.records2 is not None:
+            for k in self._FRESH_KEYS:
+                if k in d and getattr(self, k, None) is not None:
+                    getattr(self, k).copy_(d[k].to(self.device))
+            if getattr(self, "refill_every", 0):
+                self._calls = int(d.get("refill_calls", 0))
 
     def step(self, actions, auto_reset: bool = False):
         """``env.step`` (environment.py:199-213) -> (obs, reward [B], terminated [B] bool, truncated [B] bool, info).
@@ -351,6 +477,15 @@ class BatchedRaysEnv:
             terminated = self.terminated.bool()
             truncated = (self.state[:, 25] >= self.max_episode_steps) & ~terminated
             return obs, self.reward.clone(), terminated, truncated, {"success": (self.state[:, 7].to(torch.int64) & 4) != 0}
+        if self.records2 is not None:
+            if int(self.max_episode_steps) <= 0:
+                raise MpcGpuError("max_episode_steps must be positive")
+            self._fresh_launch(actions, int(self.max_episode_steps))
+            if getattr(self, "refill_every", 0):
+                self._calls += 1
+                if self._calls % self.refill_every == 0:
+                    self.refill()
+            return self._autoreset_result()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
         if actions.shape != (self.B,):
@@ -362,6 +497,10 @@ class BatchedRaysEnv:
             self.term_external.data_ptr(), int(self.max_episode_steps), stream)
         if rc != 0:
             raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
+        return self._autoreset_result()
+
+    def _autoreset_result(self):
+        torch = self._torch
         obs = self._obs()
         terminated, truncated = self.terminated.bool(), self.truncated.bool()
         done = terminated | truncated
@@ -462,6 +601,12 @@ class BatchedImgsEnv(BatchedRaysEnv):
         self.term_image = torch.zeros_like(self.obs_image)
         self.distance_field = torch.from_numpy(image_distance_field(W, H, image_scale_x, image_scale_y, image_center_x,
                                                                     image_center_y)).to(self.device).contiguous()
+
+    def enable_spares(self) -> None:
+        raise NotImplementedError("map turnover is built for the ray environment only: the image kernel has no fresh-map variant")
+
+    def enable_fresh_maps(self, seed: int = 0, refill_every: int = 16) -> None:
+        raise NotImplementedError("map turnover is built for the ray environment only: the image kernel has no fresh-map variant")
 
     def _launch(self, actions) -> None:
         torch = self._torch
