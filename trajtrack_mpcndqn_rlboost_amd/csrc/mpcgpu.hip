@@ -3,6 +3,7 @@
 // Host side only: argument validation, device buffers, workspace + LDS layout, launches, timing events.
 // No CPU fallback: every entry point needs a HIP device.
 #include "../../include/mpcgpu.h"
+#include "../../include/mpcgpu_fleet.h"
 #include "mpc_kernels.hpp"
 #include "mpc_team.hpp"
 #include "mpc_tracker.hpp"
@@ -47,6 +48,7 @@ struct Handle {
     DevBuf ws, counts, evals, perm, bins, nlist, ylist, trace, p, u0, y0, c0, u, cost, status, inner, outer, fpr, f2, y, ms, xi, psi, f, grad, F1, F2;
     int order = 1;      // MPCGPU_OPT_ORDER: 0 problems are dispatched as given, 1 longest first by the previous call's evaluation counts
     int evals_B = 0;    // batch size of the call whose evaluation counts `evals` holds (0: none)
+    const void* evals_rows = nullptr;  // ... and the row list of that call (fleet form of the tracker tick; NULL: problem j is robot j).  Compared only
     int last_ordered = 0;  // the last throughput launch used a permutation
     int* h_counts = nullptr;  // pinned
     int last_shape[4] = {0, 0, 0, 0};
@@ -326,12 +328,18 @@ TrackerView tracker_view(const Handle* h, const mpcgpu_tracker* t) {
     v.idx_ref = t->idx_ref; v.stc = t->stc; v.dyn = t->dyn; v.other = t->other; v.pred_states = t->pred_states; v.active = t->active;
     for (int i = 0; i < 10; ++i) v.tuning[i] = t->tuning[i];
     v.base_speed = t->base_speed; v.low_speed = t->low_speed; v.stc_weight = t->stc_weight; v.dyn_weight = t->dyn_weight;
+    v.rows = nullptr; v.arrived = nullptr; v.n = t->B; v.stop_when_done = 1;   // the plain tick
     return v;
+}
+// the tracker's assembly for the B problems of a launch: the plain tick runs the instantiation without the row list
+void launch_tracker_assemble(Handle* h, const TrackerView& tv, int B, const double* refs, double* ws, int* counts, hipStream_t s) {
+    if (fleet_form(tv)) hipLaunchKernelGGL(tracker_assemble_kernel<true>, dim3(B), dim3(WAVE), 0, s, h->kp, tv, refs, ws, counts);
+    else hipLaunchKernelGGL(tracker_assemble_kernel<false>, dim3(B), dim3(WAVE), 0, s, h->kp, tv, refs, ws, counts);
 }
 
 // `trk` != NULL: the compact records come from the tracker's arrays (tracker_assemble_kernel) instead of parameter vectors
 int prepare(Handle* h, int B, const double* d_p, hipStream_t s, BatchPtrs& io, bool allow_reserved,
-            const mpcgpu_tracker* trk = nullptr, const double* refs = nullptr) {
+            const TrackerView* trk = nullptr, const double* refs = nullptr) {
     if (int r = ensure(h, h->ws, (size_t)B * h->kp.ws_stride * sizeof(double))) return r;
     if (int r = ensure(h, h->counts, CNT_WORDS * sizeof(int))) return r;
     io.p = d_p;
@@ -339,7 +347,7 @@ int prepare(Handle* h, int B, const double* d_p, hipStream_t s, BatchPtrs& io, b
     io.counts = (int*)h->counts.ptr;
     HIP_OK(h, hipMemsetAsync(io.counts, 0, CNT_WORDS * sizeof(int), s));
     if (!h->capturing) HIP_OK(h, hipEventRecord(h->ev[0], s));
-    if (trk) hipLaunchKernelGGL(tracker_assemble_kernel, dim3(B), dim3(WAVE), 0, s, h->kp, tracker_view(h, trk), refs, io.ws, io.counts);
+    if (trk) launch_tracker_assemble(h, *trk, B, refs, io.ws, io.counts, s);
     else hipLaunchKernelGGL(prep_kernel, dim3(B), dim3(WAVE), 0, s, h->kp, io, B);
     HIP_OK(h, hipGetLastError());
     if (!h->capturing) HIP_OK(h, hipEventRecord(h->ev[1], s));
@@ -483,8 +491,9 @@ int32_t mpcgpu_num_params(void* handle) {
 
 namespace {
 // One batched solve enqueued on `s`.  The problems come either as parameter vectors `p` (the plugin boundary) or from the
-// device-resident tracker state `trk` + the references `refs` its robots track this tick.
-int32_t solve_common(Handle* h, int32_t B, const double* p, const mpcgpu_tracker* trk, const double* refs, const double* u0,
+// device-resident tracker state `trk` + the references `refs` its robots track this tick (B = trk->n problems: all robots, or
+// the robots of trk->rows).
+int32_t solve_common(Handle* h, int32_t B, const double* p, const TrackerView* trk, const double* refs, const double* u0,
                      const double* y0, const double* c0, double* u, double* cost, int32_t* status, int32_t* inner_it,
                      int32_t* outer_it, double* fpr, double* f2norm, double* y_out, double* ms, hipStream_t s) {
     InCall in_call_mark(h);
@@ -494,6 +503,11 @@ int32_t solve_common(Handle* h, int32_t B, const double* p, const mpcgpu_tracker
     const bool same_stream_as_last = h->last_stream == s && h->last_B > 0;
     h->last_stream = s;
     h->last_captured = h->capturing;
+    // ... and only when it solved the same problems: the counts are indexed by problem, and problem j of a tracker tick over a row
+    // list is robot rows[j].  Two colours of a fleet tick have different lists, so their counts say nothing about each other (the
+    // order they would give is still a permutation: it could cost time, never results).
+    const void* rows_now = trk ? (const void*)trk->rows : nullptr;
+    const bool same_rows_as_last = h->evals_rows == rows_now;
     BatchPtrs io{};
     // Small batches take the latency kernel: one problem per workgroup of four wavefronts, compaction fused, carve from the
     // configured maxima -- one launch, nothing read back.  Results are bitwise those of the throughput kernel.
@@ -532,7 +546,7 @@ int32_t solve_common(Handle* h, int32_t B, const double* p, const mpcgpu_tracker
     }
     auto team_done = [&](const KParams& kt, size_t lds_t, int tw) {
         h->last_B = B; h->last_team = tw; h->last_pairing = 0; h->last_min_waves = 1;
-        h->evals_B = B; h->last_ordered = 0;
+        h->evals_B = B; h->evals_rows = rows_now; h->last_ordered = 0;
         h->last_shape[0] = kt.mKs; h->last_shape[1] = kt.mKf; h->last_shape[2] = kt.mKd; h->last_shape[3] = (int)lds_t;
     };
     if (B <= team_cap && !use_duo(h)) {
@@ -554,7 +568,7 @@ int32_t solve_common(Handle* h, int32_t B, const double* p, const mpcgpu_tracker
             if (lds_t + PREP_STATIC_LDS <= 160 * 1024) {   // else (long horizons with many obstacle slots): the throughput kernel below
                 if (!h->capturing) HIP_OK(h, hipEventRecord(h->ev[0], s));
                 if (trk) {   // the records come from the tracker's arrays: one more (tiny) launch in front of the solve
-                    hipLaunchKernelGGL(tracker_assemble_kernel, dim3(B), dim3(WAVE), 0, s, h->kp, tracker_view(h, trk), refs, io.ws, (int*)nullptr);
+                    launch_tracker_assemble(h, *trk, B, refs, io.ws, nullptr, s);
                     HIP_OK(h, hipGetLastError());
                 }
                 if (!h->capturing) { HIP_OK(h, hipEventRecord(h->ev[1], s)); HIP_OK(h, hipEventRecord(h->ev[2], s)); }
@@ -650,7 +664,7 @@ int32_t solve_common(Handle* h, int32_t B, const double* p, const mpcgpu_tracker
         const int by_regs = 4 * (h->last_pairing ? 2 : h->last_min_waves), by_lds = (int)(160 * 1024 / wg_lds);
         resident = (by_regs < by_lds ? by_regs : by_lds) * h->num_cus * (h->last_pairing ? 2 : 1);
     }
-    if (h->order == 1 && h->evals_B == B && B > resident && same_stream_as_last) {
+    if (h->order == 1 && h->evals_B == B && B > resident && same_stream_as_last && same_rows_as_last) {
         if (int r = ensure(h, h->perm, (size_t)B * sizeof(int32_t))) return r;
         if (int r = ensure(h, h->bins, ORD_BINS * sizeof(int))) return r;
         // bin width: 1024 bins over the largest possible evaluation count (about 12 per PANOC step)
@@ -664,7 +678,7 @@ int32_t solve_common(Handle* h, int32_t B, const double* p, const mpcgpu_tracker
         io.perm = (const int32_t*)h->perm.ptr;
         h->last_ordered = 1;
     }
-    h->evals_B = B;
+    h->evals_B = B; h->evals_rows = rows_now;
     // Tail promotion (mpc_kernels.hpp YIELD): once all but K problems of this launch have finished, the wavefronts that are still
     // running leave at the start of their next inner problem and a continuation launch of the latency kernel (four wavefronts per
     // problem) finishes them -- bitwise the same results.
@@ -862,9 +876,48 @@ int32_t mpcgpu_tracker_step_dev(void* handle, const mpcgpu_tracker* t, const dou
     if (t->B == 0) return 0;
     HIP_OK(h, hipSetDevice(h->device));
     hipStream_t s = pick_stream(h, stream);
-    if (int r = solve_common(h, t->B, nullptr, t, refs, u0, nullptr, nullptr, u, cost, status, inner_it, outer_it, nullptr, nullptr,
+    const TrackerView tv = tracker_view(h, t);
+    if (int r = solve_common(h, t->B, nullptr, &tv, refs, u0, nullptr, nullptr, u, cost, status, inner_it, outer_it, nullptr, nullptr,
                              nullptr, nullptr, s)) return r;
-    HIP_OK(h, launch_tracker_apply(tracker_view(h, t), h->kp.N, h->kp.ts, (const double*)u, actions_out, s));
+    HIP_OK(h, launch_tracker_apply(tv, h->kp.N, h->kp.ts, (const double*)u, actions_out, s));
+    return 0;
+}
+
+// ---- fleet coupling on the device tracker (include/mpcgpu_fleet.h) -----------------------------------------------------------
+int32_t mpcgpu_fleet_share_dev(void* handle, int32_t B, int32_t N, const int32_t* members, const int32_t* group_start,
+                               const int32_t* group_len, const int32_t* pos, const double* pred_states, double* other, void* stream) {
+    Handle* h = (Handle*)handle;
+    if (!h) return -1;
+    if (B < 0) return fail(h, -1, "fleet_share: B=%d is negative", B);
+    if (N != h->kp.N) return fail(h, -1, "fleet_share: N=%d, the handle was created for N_hor=%d", N, h->kp.N);
+    if (!members || !group_start || !group_len || !pos || !pred_states || !other)
+        return fail(h, -1, "fleet_share: members, group_start, group_len, pos, pred_states and other must not be NULL");
+    if (B == 0 || h->kp.Nother == 0) return 0;
+    HIP_OK(h, hipSetDevice(h->device));
+    HIP_OK(h, launch_fleet_share(B, N, h->kp.Nother, members, group_start, group_len, pos, pred_states, other, pick_stream(h, stream)));
+    return 0;
+}
+
+// The tick of the robots `rows`.  What solve_common enqueues ends on `s`: a continuation of the tail promotion that ran on the side
+// stream is joined there (hipStreamWaitEvent(s, ev_join)) before the sweep launch, so the apply kernel below -- and whatever the
+// caller enqueues behind it, the next colour's share kernel reading pred_states -- comes after every solve of this colour.
+int32_t mpcgpu_tracker_step_rows_dev(void* handle, const mpcgpu_tracker* t, const int32_t* rows, int32_t n, int32_t stop_when_done,
+                                     uint8_t* arrived, const double* refs, const double* u0, double* u, double* cost, int32_t* status,
+                                     int32_t* inner_it, int32_t* outer_it, double* actions_out, void* stream) {
+    Handle* h = (Handle*)handle;
+    if (!h) return -1;
+    if (int r = check_tracker(h, t)) return r;
+    if (n < 0 || n > t->B) return fail(h, -1, "tracker_step_rows: n=%d outside 0..B=%d", n, t->B);
+    if (!rows && n != t->B) return fail(h, -1, "tracker_step_rows: rows == NULL means every robot, but n=%d and B=%d", n, t->B);
+    if (!refs || !u || !cost || !status) return fail(h, -1, "refs, u, cost and status must not be NULL");
+    if (n == 0) return 0;
+    HIP_OK(h, hipSetDevice(h->device));
+    hipStream_t s = pick_stream(h, stream);
+    TrackerView tv = tracker_view(h, t);
+    tv.rows = rows; tv.arrived = arrived; tv.n = n; tv.stop_when_done = stop_when_done != 0;
+    if (int r = solve_common(h, n, nullptr, &tv, refs, u0, nullptr, nullptr, u, cost, status, inner_it, outer_it, nullptr, nullptr,
+                             nullptr, nullptr, s)) return r;
+    HIP_OK(h, launch_tracker_apply(tv, h->kp.N, h->kp.ts, (const double*)u, actions_out, s));
     return 0;
 }
 
@@ -904,7 +957,8 @@ int32_t mpcgpu_debug_tracker_assemble(void* handle, const mpcgpu_tracker* t, con
     HIP_OK(h, hipSetDevice(h->device));
     h->capturing = false;
     BatchPtrs io{};
-    if (int r = prepare(h, t->B, nullptr, h->stream, io, false, t, refs)) return r;
+    const TrackerView tv = tracker_view(h, t);
+    if (int r = prepare(h, t->B, nullptr, h->stream, io, false, &tv, refs)) return r;
     HIP_OK(h, hipStreamSynchronize(h->stream));
     return 0;
 }

@@ -60,15 +60,25 @@ __device__ __forceinline__ void unicycle_rk4(double& x, double& y, double& th, d
     const double dt = sixth * (k1t + 2.0 * k2t + 2.0 * k3t + k4t);
     x = x + dx; y = y + dy; th = th + dt;
 }
-// one thread per robot: u [B][N][2] the solution; actions_out [B][2] the applied first input (0 for robots that are done)
+// one thread per problem: u [n][N][2] the solutions; actions_out [n][2] the applied first input (0 for robots that are done).
+// ROWS = false: the plain tick, problem b is robot b.  ROWS = true: problem j is robot rows[j] (mpc_tracker_types.hpp); u and
+// actions_out stay in problem order, the tracker arrays are robot-indexed.
+template <bool ROWS>
 __global__ __launch_bounds__(128) void tracker_apply_kernel(TrackerView t, int N, double ts, const double* __restrict__ u, double* __restrict__ actions_out) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= t.B) return;
-    const double* ub = u + (size_t)b * 2 * N;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (ROWS ? t.n : t.B)) return;
+    int b = j;
+    if constexpr (ROWS) {
+        if (t.rows) {
+            b = t.rows[j];
+            if (b < 0 || b >= t.B) return;            // a row outside the tracker (the caller's promise broken) moves nobody
+        }
+    }
+    const double* ub = u + (size_t)j * 2 * N;
     const bool act = t.active[b] != 0;
     if (!act) {                                       // get_action returns None once the termination test has fired
         t.last_actions[2 * b] = 0.0; t.last_actions[2 * b + 1] = 0.0;
-        if (actions_out) { actions_out[2 * b] = 0.0; actions_out[2 * b + 1] = 0.0; }
+        if (actions_out) { actions_out[2 * j] = 0.0; actions_out[2 * j + 1] = 0.0; }
         return;
     }
     double x = t.states[3 * b], y = t.states[3 * b + 1], th = t.states[3 * b + 2];
@@ -78,12 +88,38 @@ __global__ __launch_bounds__(128) void tracker_apply_kernel(TrackerView t, int N
     unicycle_rk4(x, y, th, ul[0], ul[1], ts);
     t.states[3 * b] = x; t.states[3 * b + 1] = y; t.states[3 * b + 2] = th;
     t.last_actions[2 * b] = ul[0]; t.last_actions[2 * b + 1] = ul[1];
-    if (actions_out) { actions_out[2 * b] = ub[0]; actions_out[2 * b + 1] = ub[1]; }
+    if (actions_out) { actions_out[2 * j] = ub[0]; actions_out[2 * j + 1] = ub[1]; }
     // prediction: rolled from the TAKEN state with the whole input sequence again (the reference re-applies u[0]: kept)
     double* pr = t.pred_states + (size_t)b * N * 3;
     for (int k = 0; k < N; ++k) {
         unicycle_rk4(x, y, th, ub[2 * k], ub[2 * k + 1], ts);
         pr[3 * k] = x; pr[3 * k + 1] = y; pr[3 * k + 2] = th;
+    }
+}
+
+// ---- get_other_robot_states for a whole fleet (src/scenario_simulator.py:154-163) -----------------------------------------------
+// one wavefront per robot: other[b] = [Nother][N][3]; slot s = pred_states of the s-th member of b's group with b itself skipped,
+// in group order; slots past the group's other members are 0.0 (every double of the block is written: nothing stale survives).
+// Group table: members [B] = the groups concatenated; group_start / group_len / pos [B] = where b's group begins in `members`,
+// how many robots it has, and b's own position in it.  Pure copies.
+__global__ __launch_bounds__(WAVE) void fleet_share_kernel(int B, int N, int Nother, const int32_t* __restrict__ members,
+                                                           const int32_t* __restrict__ group_start, const int32_t* __restrict__ group_len,
+                                                           const int32_t* __restrict__ pos, const double* __restrict__ pred_states,
+                                                           double* __restrict__ other) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const int per = 3 * N, start = group_start[b], len = group_len[b], me = pos[b];
+    const int keep = len - 1 < Nother ? len - 1 : Nother;
+    double* o = other + (size_t)b * per * Nother;
+    for (int i = lane; i < per * Nother; i += WAVE) {
+        const int s = i / per, k = i - s * per;
+        double v = 0.0;
+        if (s < keep) {
+            const int at = start + (s < me ? s : s + 1);      // < start + len <= B (checked on the host: the table is a partition)
+            const int m = members[at < 0 ? 0 : (at < B ? at : B - 1)];    // a broken table is pinned into the arrays
+            v = pred_states[(size_t)(m < 0 ? 0 : (m < B ? m : B - 1)) * per + k];
+        }
+        o[i] = v;
     }
 }
 
@@ -221,7 +257,13 @@ hipError_t launch_tracker_window(const TrackerView& t, int N, double* refs_out, 
 }
 hipError_t launch_tracker_apply(const TrackerView& t, int N, double ts, const double* u, double* actions_out, hipStream_t s) {
     const int threads = 128;
-    hipLaunchKernelGGL(tracker_apply_kernel, dim3((t.B + threads - 1) / threads), dim3(threads), 0, s, t, N, ts, u, actions_out);
+    if (fleet_form(t)) hipLaunchKernelGGL(tracker_apply_kernel<true>, dim3((t.n + threads - 1) / threads), dim3(threads), 0, s, t, N, ts, u, actions_out);
+    else hipLaunchKernelGGL(tracker_apply_kernel<false>, dim3((t.B + threads - 1) / threads), dim3(threads), 0, s, t, N, ts, u, actions_out);
+    return hipGetLastError();
+}
+hipError_t launch_fleet_share(int B, int N, int Nother, const int32_t* members, const int32_t* group_start, const int32_t* group_len,
+                              const int32_t* pos, const double* pred_states, double* other, hipStream_t s) {
+    hipLaunchKernelGGL(fleet_share_kernel, dim3(B), dim3(WAVE), 0, s, B, N, Nother, members, group_start, group_len, pos, pred_states, other);
     return hipGetLastError();
 }
 hipError_t launch_rl_reference(int B, const double* agent, int agent_stride, const int64_t* action, double ts, int steps,

@@ -10,13 +10,20 @@ window search of ``get_local_ref_traj`` (``trajectory_generator.py:206-232``) as
 robot and per field: ``update_static_constraints(i)`` rewrites robot i's half-plane rows and nothing else (it may be called at any
 time, ``src/interface_mpc.py:60-63``), ``initialization(i)`` re-plans robot i alone; the other robots keep the state the device has
 advanced them to.
+
+Fleet coupling (``include/mpcgpu_fleet.h``, :mod:`fleet`): ``set_groups`` uploads the group table once;
+``share_predictions`` is one launch of ``fleet_share_kernel`` (Jacobi when followed by a plain ``step``); ``step(groups=...)`` is
+the Gauss-Seidel tick of ``BatchedTracker.step(groups=...)`` -- per colour one share and one ``step_rows``, the tick of a row
+list.  ``stop_when_done = False`` is the multi-robot simulator's rule: the termination test only reports (``arrived``).
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional, Sequence
 
 import numpy as np
 
+from . import fleet
 from .config import MpcConfig
 from .geometry import static_obstacle_params
 from .solver import BatchSolver, CTracker
@@ -56,6 +63,12 @@ class DeviceTracker:
         self._h_states, self._h_goals = np.zeros((B, 3)), np.zeros((B, 3))
         self._h_stc = np.zeros((B, config.Nstcobs * config.nstcobs))
         self._init_rows, self._stc_rows = set(), set()      # robots whose set-up calls wait for their upload
+        # fleet coupling: the simulator's rule (BatchedTracker.stop_when_done), the termination test's last verdict, the group
+        # table (uploaded by set_groups; default: one group of all robots) and compact staging buffers of a tick over a row list
+        self.stop_when_done = True
+        self.arrived = torch.zeros(B, dtype=torch.uint8, device=self.device)
+        self._groups_src, self._table, self.colour_rows = None, None, []
+        self._stage = None
 
     def set_mode(self, mode: str):
         self.base_speed, self.tuning = work_mode(self.config, mode)
@@ -132,14 +145,111 @@ class DeviceTracker:
         self.solver.tracker_window(self.view(), self.refs, stream=self._stream(stream))
         return self.refs
 
-    def step(self, refs=None, initial_guess=None, stream: Optional[int] = None):
+    def step(self, refs=None, initial_guess=None, stream: Optional[int] = None, groups=None):
         """Enqueue the tick of all robots.  ``refs`` [B, N, 3] device tensor: the reference every robot tracks (default: its
         local window).  Returns the dict of device tensors ``u, cost, status, inner_it, outer_it, actions`` (the tracker's own
-        buffers); ``states``, ``pred_states``, ``last_actions`` and ``active`` are updated in place."""
+        buffers); ``states``, ``pred_states``, ``last_actions`` and ``active`` are updated in place.
+        ``groups`` (lists of mutually coupled robots, or ``True`` = the groups of ``set_groups``): the tick is solved
+        Gauss-Seidel over colours like ``BatchedTracker.step(groups=...)`` -- the window search once, up front, then per colour
+        one ``share_predictions`` and one ``step_rows``; ``out`` holds the whole fleet afterwards.  Not given: one solve of
+        all robots with whatever ``other`` holds (Jacobi when fed by ``share_predictions``)."""
+        if groups is not None:
+            if groups is not True:
+                self.set_groups(groups)
+            elif self._table is None:
+                self.set_groups(None)
         if refs is None:
             refs = self.local_refs(stream)
-        self.solver.tracker_step(self.view(), refs, self.out, initial_guess=initial_guess, stream=self._stream(stream))
+        if groups is not None:
+            for c in range(len(self.colour_rows)):
+                self.share_predictions(stream=stream)
+                self._step_rows(self.colour_rows[c], refs, initial_guess, stream)
+            return self.out
+        if self.stop_when_done:
+            self.solver.tracker_step(self.view(), refs, self.out, initial_guess=initial_guess, stream=self._stream(stream))
+        else:
+            self._step_rows(None, refs, initial_guess, stream)
         return self.out
+
+    # -- fleet coupling --------------------------------------------------------------------------------------------------
+    def set_groups(self, groups):
+        """Upload the group table (``fleet.pack_groups``; ``None`` = one group of all robots).  ``ValueError`` unless the groups
+        partition the robots.  The same object passed again is not packed again."""
+        if self._table is not None and groups is self._groups_src:
+            return
+        torch = self._torch
+        table = fleet.pack_groups(groups, self.B)
+        dev = [torch.from_numpy(a).to(self.device) for a in (table.members, table.group_start, table.group_len, table.pos)]
+        rows = [torch.from_numpy(c).to(self.device) for c in table.colours]
+        self._table, self._groups_src = dev, groups
+        self.colour_rows = [(r, r.long()) for r in rows]     # int32 for the kernels, int64 for index_copy_
+
+    def share_predictions(self, groups=None, stream: Optional[int] = None):
+        """``BatchedTracker.share_predictions`` as one launch: every robot's ``other`` block from the latest ``pred_states`` of
+        its group.  ``groups``: as ``set_groups`` (default: the table already set)."""
+        if groups is not None or self._table is None:
+            self.set_groups(groups)
+        members, start, length, pos = self._table
+        rc = fleet._bind(self.solver._L).mpcgpu_fleet_share_dev(self.solver._h, self.B, int(self.config.N_hor), members.data_ptr(),
+                                                    start.data_ptr(), length.data_ptr(), pos.data_ptr(),
+                                                    self.pred_states.data_ptr(), self.other.data_ptr(), self._stream(stream))
+        self.solver._check(rc, "mpcgpu_fleet_share_dev")
+
+    def step_rows(self, rows, refs=None, initial_guess=None, stream: Optional[int] = None):
+        """The tick of the robots ``rows`` (one colour): problem j is robot ``rows[j]``.  ``rows``: distinct robots in 0..B-1
+        (a sequence or array; ``ValueError`` before anything is enqueued otherwise) or an entry of ``colour_rows``.  ``refs``
+        [B, N, 3], robot-indexed (default: the window of the last ``local_refs`` call -- the window search is NOT run again: a
+        colour must not advance the indices of the colours before it a second time); ``initial_guess`` [B, 2N], robot-indexed.
+        The results are scattered into the robot-indexed ``out``; the other robots' entries keep what they held."""
+        if isinstance(rows, tuple) and any(rows is c for c in self.colour_rows):
+            pair = rows
+        else:
+            torch = self._torch
+            if torch.is_tensor(rows):
+                rows = rows.cpu().numpy()
+            r32 = torch.from_numpy(fleet.check_rows(rows, self.B)).to(self.device)
+            pair = (r32, r32.long())
+        self._step_rows(pair, self.refs if refs is None else refs, initial_guess, stream)
+        return self.out
+
+    def _step_rows(self, pair, refs, initial_guess, stream):
+        torch = self._torch
+        st = self._stream(stream)
+
+        def ptr(t):
+            return None if t is None else t.data_ptr()
+        if pair is None:                                    # every robot, in order: straight into `out`
+            rows32, n, dst = None, self.B, self.out
+        else:
+            rows32, rows64 = pair
+            n = int(rows32.shape[0])
+            if n == 0:
+                return
+            if self._stage is None:
+                self._stage = {k: torch.zeros_like(v) for k, v in self.out.items()}
+                self._stage["u0"] = torch.zeros_like(self.out["u"])
+            dst = {k: v[:n] for k, v in self._stage.items()}
+        with self._torch_stream(st):
+            if initial_guess is not None and pair is not None:
+                torch.index_select(initial_guess, 0, rows64, out=dst["u0"])
+                initial_guess = dst["u0"]
+            rc = fleet._bind(self.solver._L).mpcgpu_tracker_step_rows_dev(
+                self.solver._h, C.byref(self.view()), ptr(rows32), n, 1 if self.stop_when_done else 0, self.arrived.data_ptr(), ptr(refs),
+                ptr(initial_guess), ptr(dst["u"]), ptr(dst["cost"]), ptr(dst["status"]), ptr(dst["inner_it"]), ptr(dst["outer_it"]),
+                ptr(dst["actions"]), st)
+            self.solver._check(rc, "mpcgpu_tracker_step_rows_dev")
+            if pair is not None:
+                for k, v in self.out.items():
+                    v.index_copy_(0, rows64, dst[k])
+
+    def _torch_stream(self, raw):
+        """Context in which torch enqueues on the raw stream ``raw`` (the gather of the initial guess and the scatter of the
+        results belong on the stream of the tick)."""
+        torch = self._torch
+        if raw == torch.cuda.current_stream().cuda_stream:
+            import contextlib
+            return contextlib.nullcontext()
+        return torch.cuda.stream(torch.cuda.ExternalStream(raw, device=self.device))
 
     def _stream(self, stream):
         return self._torch.cuda.current_stream().cuda_stream if stream is None else stream
