@@ -31,6 +31,15 @@ extern "C" {
 
 #define MPCGPU_ABI_VERSION 8
 
+/* Edges of a static obstacle: nstcobs = 3 x edges, mpc_generator.py:221 (n_edges = nstcobs / 3), slot layout b[ne] | a0[ne] | a1[ne]
+ * (:222).  Accepted: 4 .. 8 edges, i.e. nstcobs = 12, 15, 18, 21 or 24.  Four is the floor because a polygon with fewer edges is
+ * not a config of its own: it fills a slot with neutral half-planes (b, a0, a1) = (1, 0, 0), which multiply the polygon product by
+ * exactly 1.  Eight is the ceiling: it keeps the static table of a problem below 2 KB of LDS (Nstcobs <= 10 in the reference's
+ * configs x 24 doubles = 1920 B), and an octagon covers round pillars.  nstcobs = 12 runs the kernels with a compiled horizon
+ * (N_hor = 20, 40); every other width runs the generic-horizon kernels at any N_hor. */
+#define MPCGPU_MIN_EDGES 4
+#define MPCGPU_MAX_EDGES 8
+
 /* replaces: the yaml config consumed by MpcModule.build (mpc_generator.py:151-158, config/mpc_default.yaml:7-55)
  * plus the SolverConfiguration of mpc_generator.py:285-293 (opengen defaults quoted there). */
 typedef struct mpcgpu_config {
@@ -39,7 +48,7 @@ typedef struct mpcgpu_config {
     int32_t ns;       /* 3 */
     int32_t Nother;   /* max other robots        (<= 16) */
     int32_t Nstcobs;  /* max static obstacles    (<= 16) */
-    int32_t nstcobs;  /* 12 = 4 edges x (b,a0,a1) */
+    int32_t nstcobs;  /* 3 x edges x (b,a0,a1): 12, 15, 18, 21 or 24 (MPCGPU_MIN_EDGES .. MPCGPU_MAX_EDGES) */
     int32_t Ndynobs;  /* max dynamic obstacles   (1..32) */
     int32_t ndynobs;  /* 6 = (x,y,rx,ry,angle,alpha) */
     double ts;
@@ -320,7 +329,7 @@ typedef struct mpcgpu_tracker {
     const double* ref;         /* [B][ref_cap][3] global reference trajectories (get_global_ref_traj), padded */
     const int32_t* ref_len;    /* [B] */
     int32_t* idx_ref;          /* [B] in/out */
-    const double* stc;         /* [B][Nstcobs * 12]      static half-plane rows (update_static_constraints) */
+    const double* stc;         /* [B][Nstcobs * nstcobs] static half-plane rows (update_static_constraints) */
     const double* dyn;         /* [B][Ndynobs * 6 * N]   dynamic rows (update_dynamic_constraints) */
     const double* other;       /* [B][3 * N * Nother] other robots' predictions, or NULL = zeros */
     double* pred_states;       /* [B][N][3] out */

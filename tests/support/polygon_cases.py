@@ -1,0 +1,96 @@
+"""Scenes with static obstacles of 3 .. 8 edges for the polygon-edge tests (tests/test_polygon_edges_host.py on the CPU,
+tests/test_gpu_polygon_edges.py on the GPU): convex hulls laid across the rollouts of given input sequences, and an inflated
+hexagon on the reference path.  Everything is seeded and built on the CPU; the tests check by the oracle's values that the
+scenes hold what they are meant to hold."""
+import numpy as np
+
+from trajtrack_mpcndqn_rlboost_amd import scenes
+
+INFLATE = 0.8          # the reference's inflation of static obstacles (src/main.py:110)
+
+
+def rollout(start, u, ts):
+    """Positions [B, N, 2] after every step of the unicycle under piecewise-constant inputs u [B, 2N] = (v_0, w_0, v_1, ...):
+    RK4 with constant inputs (motion_model.py:142-164) is Simpson's rule on the heading."""
+    B = u.shape[0]
+    v, w = u.reshape(B, -1, 2)[..., 0], u.reshape(B, -1, 2)[..., 1]
+    th1 = start[:, 2:3] + ts * np.cumsum(w, axis=1)
+    th0 = th1 - ts * w
+    thm = th0 + 0.5 * ts * w
+    dx = ts * v * (np.cos(th0) + 4.0 * np.cos(thm) + np.cos(th1)) / 6.0
+    dy = ts * v * (np.sin(th0) + 4.0 * np.sin(thm) + np.sin(th1)) / 6.0
+    return np.stack([start[:, 0:1] + np.cumsum(dx, axis=1), start[:, 1:2] + np.cumsum(dy, axis=1)], axis=-1)
+
+
+def convex_polygon(rng, centre, nv, radius, regular):
+    """nv vertices in counter-clockwise order: a regular polygon, or points at irregular angles on a rotated ellipse (any such
+    set is in convex position: the hull has exactly nv edges)."""
+    if regular:
+        ang = rng.uniform(0, 2 * np.pi) + 2 * np.pi * np.arange(nv) / nv
+        ax, ay, rot = radius, radius, 0.0
+    else:
+        gaps = rng.uniform(0.6, 1.4, nv)
+        ang = rng.uniform(0, 2 * np.pi) + 2 * np.pi * np.cumsum(gaps) / gaps.sum()
+        ax, ay, rot = radius * rng.uniform(0.7, 1.3), radius * rng.uniform(0.7, 1.3), rng.uniform(0, np.pi)
+    x, y = ax * np.cos(ang), ay * np.sin(ang)
+    return np.stack([centre[0] + x * np.cos(rot) - y * np.sin(rot), centre[1] + x * np.sin(rot) + y * np.cos(rot)], axis=-1)
+
+
+def hull_scene(cfg, B, u, seed, n_dyn=4, n_other=1):
+    """make_batch without walls and box; problem i uses 0, 1 or all Nstcobs static slots (i % 3), every used slot holds a regular or
+    an irregular convex polygon with 3 .. nstcobs / 3 edges (narrower hulls padded: padded and full hulls side by side in one
+    problem).  In every other problem that has polygons, one of them is centred on a point of the rollout of u[i]; the others stand
+    3.5 .. 6 m from every rollout point of their problem."""
+    ne = int(cfg.nstcobs) // 3
+    sc = scenes.make_batch(cfg, B, n_dyn=n_dyn, n_other=n_other, with_walls=False, with_box=False, seed=seed)
+    p, off = sc["p"], cfg.offsets()
+    rng = np.random.default_rng(seed + 1)
+    pos = rollout(sc["start"], u, cfg.ts)
+    slots_used = np.array([(0, 1, int(cfg.Nstcobs))[i % 3] for i in range(B)])
+    for i in range(B):
+        hit = (i // 3) % 2 == 0
+        for o in range(slots_used[i]):
+            nv = ne if o % 2 == 0 else int(rng.integers(3, ne + 1))
+            radius = rng.uniform(0.6, 1.4)
+            if hit and o == 0:
+                k = int(rng.integers(0, pos.shape[1]))
+                centre = pos[i, k] + rng.uniform(-0.15, 0.15, 2)
+            else:
+                mid = pos[i, pos.shape[1] // 2]
+                reach = np.max(np.hypot(*(pos[i] - mid).T))
+                phi = rng.uniform(0, 2 * np.pi)
+                centre = mid + (reach + 1.3 * 1.4 + rng.uniform(3.5, 6.0)) * np.array([np.cos(phi), np.sin(phi)])
+            verts = convex_polygon(rng, centre, nv, radius, regular=bool(rng.integers(0, 2)))
+            p[i, off["os"] + o * 3 * ne: off["os"] + (o + 1) * 3 * ne] = scenes.polygon_halfspaces(verts, ne)
+    return sc, slots_used
+
+
+def hexagon_scene(cfg, B, seed, nv=6, radius=(0.5, 0.9), depth=(-0.8, 0.25), **family):
+    """A corridor-free scene with ONE inflated regular polygon of nv edges near the reference path: its inflated hull reaches
+    `depth` metres over the path (negative: it stands beside it).  Returns (scene dict, vertices [B, nv, 2])."""
+    ne = int(cfg.nstcobs) // 3
+    kw = dict(n_dyn=0, with_walls=False, with_box=False, v_init_range=(1.0, 1.2), on_track=True)
+    kw.update(family)
+    sc = scenes.make_batch(cfg, B, seed=seed, **kw)
+    p, off, ref = sc["p"], cfg.offsets(), sc["ref"]
+    rng = np.random.default_rng(seed + 1)
+    N = ref.shape[1]
+    verts = np.zeros((B, nv, 2))
+    for i in range(B):
+        k = int(rng.integers(min(10, N - 1), min(15, N - 1) + 1))
+        r = rng.uniform(*radius) + INFLATE
+        apothem = r * np.cos(np.pi / nv)
+        side = 1.0 if rng.random() < 0.5 else -1.0
+        lat = side * (apothem - rng.uniform(*depth))
+        th = ref[i, k, 2]
+        centre = ref[i, k, :2] + lat * np.array([-np.sin(th), np.cos(th)])
+        ang = th + np.pi / 2 + np.pi / nv + 2 * np.pi * np.arange(nv) / nv     # an edge (not a vertex) faces the path
+        verts[i] = centre + r * np.stack([np.cos(ang), np.sin(ang)], axis=-1)
+        p[i, off["os"]: off["os"] + 3 * ne] = scenes.polygon_halfspaces(verts[i], ne)
+    return sc, verts
+
+
+def smallest_halfplane_value(rows, ne, pts):
+    """min_e (b_e - a0_e x - a1_e y) of one slot at points [..., 2]: > 0 exactly inside the polygon."""
+    b, a0, a1 = rows[:ne], rows[ne:2 * ne], rows[2 * ne:3 * ne]
+    return np.min(b - a0 * pts[..., 0:1] - a1 * pts[..., 1:2], axis=-1)

@@ -1,0 +1,232 @@
+"""CPU: static obstacles with 4 .. 8 edges (yaml key nstcobs = 12 .. 24) -- the oracle's generic polygon branch against an
+independent restatement, the host feeders with their neutral padding rows, and which configs mpcgpu_create accepts.
+
+Only four edges are pinned by reference fixtures (tests/golden/costgrad_*.npz), so the generic loop of oracle/mpc_oracle.c:185-203
+-- the yardstick of tests/test_gpu_polygon_edges.py -- is held here against mpc_generator.py:46-54,219-225 restated in numpy."""
+import numpy as np
+import pytest
+
+import oracle
+from conftest import GROWING_PENALTY, load_golden, make_cfg, oracle_cfg
+from support import polygon_cases
+from trajtrack_mpcndqn_rlboost_amd import BatchSolver, MpcConfig, MpcGpuError, geometry, scenes
+from trajtrack_mpcndqn_rlboost_amd.batched_tracker import BatchedTracker
+from trajtrack_mpcndqn_rlboost_amd.interface_mpc import InterfaceMpc
+
+NEUTRAL = (1.0, 0.0, 0.0)
+
+
+# ---- mpc_generator.py:46-54 (inside_pollygon) and :219-225 (the sum over slots and steps), restated
+def inside_polygon(x, y, b, a0, a1):
+    result = a0 * (-x) + a1 * (-y) + b * 1.0          # mtimes(horzcat(a0, a1, b), vertcat(-x, -y, 1))
+    is_inside = 1.0
+    for r in result:
+        is_inside *= max(0.0, r) ** 2
+    return is_inside
+
+
+def static_penalty(cfg, p, points):
+    ne = int(cfg.nstcobs / 3)
+    o_s = p[cfg.offsets()["os"]:cfg.offsets()["od"]]
+    total = 0.0
+    for x, y in points:
+        for i in range(cfg.Nstcobs):
+            eq = o_s[i * cfg.nstcobs:(i + 1) * cfg.nstcobs]
+            total += max(0.0, inside_polygon(x, y, eq[:ne], eq[ne:2 * ne], eq[2 * ne:]))
+    return total
+
+
+def _standing_robot(cfg, x, y):
+    """A parameter vector whose robot stands still at (x, y) under u = 0: every rollout point IS (x, y), exactly."""
+    sc = scenes.make_batch(cfg, 1, n_dyn=2, with_walls=False, with_box=False, seed=5)
+    p = sc["p"][0].copy()
+    p[0], p[1] = x, y
+    return p
+
+
+def _exact_slot(ne):
+    """Half-planes with exactly representable coefficients around (8, 4): x < 10, x > 6, y < 6, y > 2, then cuts through the
+    corners; b = a . centre + 1.  A point with x = 10 lies ON the first edge: 5 - 0.5 * 10 is 0 in every evaluation order."""
+    a = [(0.5, 0.0), (-0.5, 0.0), (0.0, 0.5), (0.0, -0.5), (0.375, 0.375), (-0.375, 0.375), (-0.375, -0.375), (0.375, -0.375)][:ne]
+    a0, a1 = np.array([r[0] for r in a]), np.array([r[1] for r in a])
+    return np.concatenate([a0 * 8.0 + a1 * 4.0 + 1.0, a0, a1])
+
+
+@pytest.mark.parametrize("ne", [5, 6, 8])
+def test_oracle_generic_polygon_branch_matches_the_restated_reference(ne):
+    cfg = make_cfg(20, nstcobs=3 * ne)
+    ocfg = oracle_cfg(cfg)
+    off = cfg.offsets()
+    rng = np.random.default_rng(ne)
+    slots = [_exact_slot(ne),
+             scenes.polygon_halfspaces(polygon_cases.convex_polygon(rng, (8.3, 4.4), ne, 1.6, regular=True), ne),
+             scenes.polygon_halfspaces(polygon_cases.convex_polygon(rng, (7.6, 3.7), ne, 1.9, regular=False), ne),
+             scenes.polygon_halfspaces(polygon_cases.convex_polygon(rng, (8.0, 4.0), ne - 2, 1.5, regular=False), ne)]
+    # inside all, inside some, outside all, on an edge of the first slot (x = 10) and on one of its corners
+    points = [(8.0, 4.0), (8.4, 4.3), (7.1, 3.2), (9.2, 4.9), (6.3, 5.8), (9.9, 2.2), (12.5, 4.0), (8.0, 9.0), (3.0, 1.0),
+              (10.0, 4.5), (10.0, 2.0), (9.999, 4.5), (10.001, 4.5)]
+    n_in = n_out = 0
+    u = np.zeros(40)
+    for x, y in points:
+        p = _standing_robot(cfg, x, y)
+        p[off["os"]:off["os"] + len(slots) * 3 * ne] = np.concatenate(slots)
+        p0 = p.copy()
+        p0[off["os"]:off["od"]] = 0.0
+        with_block = oracle.cost_grad(ocfg, u, p, 10.0)["F2"]
+        without = oracle.cost_grad(ocfg, u, p0, 10.0)["F2"]
+        got = with_block - without                                 # F2_i = S + D_i (mpc_generator.py:225,239): the static part
+        want = static_penalty(cfg, p, [(x, y)] * 20)
+        assert np.all(got == got[0])
+        assert abs(got[0] - want) <= 1e-12 * abs(want), (x, y, got[0], want)
+        n_in += want > 0.0
+        n_out += want == 0.0
+    assert n_in >= 5 and n_out >= 5
+    assert static_penalty(cfg, np.r_[np.zeros(off["os"]), _exact_slot(ne), np.zeros(cfg.num_params)], [(10.0, 4.5)]) == 0.0
+
+
+@pytest.mark.parametrize("ne", [5, 6, 8])
+def test_oracle_gradient_with_generic_polygons_matches_central_differences(ne):
+    cfg = make_cfg(20, nstcobs=3 * ne)
+    ocfg = oracle_cfg(cfg)
+    B = 6
+    rng = np.random.default_rng(40 + ne)
+    u = np.stack([rng.uniform(0.2, 1.4, (B, 20)), rng.uniform(-0.4, 0.4, (B, 20))], axis=2).reshape(B, 40)
+    sc, used = polygon_cases.hull_scene(cfg, B, u, seed=70 + ne)
+    crossed = 0
+    for i in range(B):
+        o = oracle.cost_grad(ocfg, u[i], sc["p"][i], 10.0)
+        crossed += bool(used[i]) and float(np.min(o["F2"])) > 0.0
+        h = 1e-6
+        num = np.zeros(40)
+        for j in range(40):
+            e = np.zeros(40); e[j] = h
+            num[j] = (oracle.cost_grad(ocfg, u[i] + e, sc["p"][i], 10.0)["psi"]
+                      - oracle.cost_grad(ocfg, u[i] - e, sc["p"][i], 10.0)["psi"]) / (2 * h)
+        assert np.max(np.abs(num - o["grad"])) <= 1e-6 * max(1.0, np.max(np.abs(o["grad"]))), i
+    assert crossed >= 1                                             # some rollout runs through a polygon: the term is in the gradient
+
+
+# ---- feeders
+HEXAGON = [(4.0, 2.0), (5.0, 2.0), (5.5, 3.0), (5.0, 4.0), (4.0, 4.0), (3.5, 3.0)]
+QUAD = [(6.7, 2.2), (9.3, 2.2), (9.3, 4.8), (6.7, 4.8)]
+TRIANGLE = [(0.0, 0.0), (2.0, 0.0), (1.0, 2.0)]
+
+
+def _check_rows(rows, ne, polygon, n_real):
+    """Every vertex lies on its two edges (value 0) and inside the others; the centre has the value 1 in every row."""
+    b, a0, a1 = np.array(rows[:ne]), np.array(rows[ne:2 * ne]), np.array(rows[2 * ne:3 * ne])
+    v = np.array(polygon, dtype=float)
+    h = b[None, :n_real] - np.outer(v[:, 0], a0[:n_real]) - np.outer(v[:, 1], a1[:n_real])
+    assert np.all(np.sum(np.abs(h) < 1e-12, axis=1) == 2) and np.all(h > -1e-12)
+    c = v.mean(axis=0)
+    assert np.allclose(b - a0 * c[0] - a1 * c[1], 1.0, rtol=0, atol=1e-12)
+    assert [tuple(r) for r in zip(b[n_real:], a0[n_real:], a1[n_real:])] == [NEUTRAL] * (ne - n_real)
+
+
+def test_static_obstacle_params_and_polygon_halfspaces_pad_with_neutral_rows():
+    rows = geometry.static_obstacle_params([HEXAGON], 3, 18)
+    assert len(rows) == 54 and rows[18:] == [0.0] * 36
+    _check_rows(rows[:18], 6, HEXAGON, 6)
+    rows = geometry.static_obstacle_params([QUAD, HEXAGON], 3, 18, pad_edges=True)
+    _check_rows(rows[:18], 6, QUAD, 4)
+    _check_rows(rows[18:36], 6, HEXAGON, 6)
+    assert rows[:4] + rows[6:10] + rows[12:16] == geometry.static_obstacle_params([QUAD], 1, 12)     # the quad's own rows, bit for bit
+    rows = geometry.static_obstacle_params([TRIANGLE], 2, 12, pad_edges=True)
+    _check_rows(rows[:12], 4, TRIANGLE, 3)
+    with pytest.raises(ValueError, match="hull edges"):
+        geometry.static_obstacle_params([TRIANGLE], 2, 12)                   # the default mode pads nothing
+    with pytest.raises(ValueError, match="hull edges"):
+        geometry.static_obstacle_params([QUAD], 2, 18)
+    for pad in (False, True):
+        with pytest.raises(ValueError, match="hull edges"):
+            geometry.static_obstacle_params([HEXAGON], 2, 12, pad_edges=pad)
+    # scenes.polygon_halfspaces: the same normalisation from ordered vertices, batched, either orientation
+    for poly, ne in ((HEXAGON, 6), (QUAD, 6), (TRIANGLE, 4), (HEXAGON, 8)):
+        got = scenes.polygon_halfspaces(poly, ne)
+        _check_rows(got, ne, poly, len(poly))
+        _check_rows(scenes.polygon_halfspaces(poly[::-1], ne), ne, poly[::-1], len(poly))
+    both = scenes.polygon_halfspaces(np.array([HEXAGON, HEXAGON[::-1]]), 7)
+    assert both.shape == (2, 21) and np.array_equal(both[0], scenes.polygon_halfspaces(HEXAGON, 7))
+    want = np.array(geometry.static_obstacle_params([HEXAGON], 1, 18)).reshape(3, 6)
+    got = scenes.polygon_halfspaces(HEXAGON, 6).reshape(3, 6)
+    order = [int(np.argmin(np.abs(got[1] - a) + np.abs(got[2] - c))) for a, c in zip(want[1], want[2])]
+    assert sorted(order) == list(range(6)) and np.allclose(got[:, order], want, rtol=1e-13, atol=1e-13)   # the hull's facets, in Qhull's order
+    with pytest.raises(ValueError, match="does not fit"):
+        scenes.polygon_halfspaces(HEXAGON, 5)
+    with pytest.raises(ValueError, match="does not fit"):
+        scenes.pad_halfspaces(np.zeros(18), 5)
+
+
+def test_public_classes_pass_the_padding_keyword_on():
+    cfg = make_cfg(20, nstcobs=18)
+    want = geometry.static_obstacle_params([QUAD, HEXAGON], cfg.Nstcobs, 18, pad_edges=True)
+    bt = BatchedTracker(cfg, 2, solver=object())
+    bt.update_static_constraints(1, [QUAD, HEXAGON], pad_edges=True)
+    assert bt.stc_constraints.shape == (2, cfg.Nstcobs * 18) and bt.stc_constraints[1].tolist() == want
+    with pytest.raises(ValueError, match="hull edges"):
+        bt.update_static_constraints(0, [QUAD])
+    mpc = InterfaceMpc(cfg, solver=object())                      # the feeder part never calls the solver
+    mpc.update_static_constraints([QUAD, HEXAGON], pad_edges=True)
+    assert mpc._stc.tolist() == want
+    with pytest.raises(ValueError, match="hull edges"):
+        mpc.update_static_constraints([QUAD])
+
+
+def test_make_batch_is_unchanged_at_twelve_and_pads_its_quads_elsewhere():
+    cfg = make_cfg(20)
+    sc = scenes.make_batch(cfg, 4, n_dyn=3, seed=11, n_other=1)
+    assert sc["p"].tobytes() == load_golden("make_batch_nstcobs12.npz")["p"].tobytes()        # recorded before the slot width became a config value
+    cfg18 = make_cfg(20, nstcobs=18)
+    p18 = scenes.make_batch(cfg18, 4, n_dyn=3, seed=11, n_other=1)["p"]
+    o12, o18 = cfg.offsets(), cfg18.offsets()
+    assert np.array_equal(p18[:, :o18["os"]], sc["p"][:, :o12["os"]]) and np.array_equal(p18[:, o18["od"]:], sc["p"][:, o12["od"]:])
+    s12 = sc["p"][:, o12["os"]:o12["od"]].reshape(4, cfg.Nstcobs, 3, 4)
+    s18 = p18[:, o18["os"]:o18["od"]].reshape(4, cfg.Nstcobs, 3, 6)
+    assert np.array_equal(s18[:, :, :, :4], s12)
+    assert np.all(s18[:, :5, 0, 4:] == 1.0) and np.all(s18[:, :5, 1:, 4:] == 0.0) and np.all(s18[:, 5:] == 0.0)
+
+
+def test_oracle_treats_padded_quads_bitwise_like_the_four_edge_config():
+    cfg12, cfg18 = make_cfg(20), make_cfg(20, nstcobs=18)
+    B = 16
+    a = scenes.make_batch(cfg12, B, n_dyn=4, seed=23)["p"]
+    b = scenes.make_batch(cfg18, B, n_dyn=4, seed=23)["p"]
+    rng = np.random.default_rng(23)
+    u = np.stack([rng.uniform(-0.7, 1.8, (B, 20)), rng.uniform(-0.7, 0.7, (B, 20))], axis=2).reshape(B, 40)
+    inside = 0
+    for i in range(B):
+        ra = oracle.cost_grad(oracle_cfg(cfg12), u[i], a[i], 10.0)
+        rb = oracle.cost_grad(oracle_cfg(cfg18), u[i], b[i], 10.0)
+        for k in ("f", "psi", "grad", "F2"):
+            assert np.array_equal(ra[k], rb[k]), (i, k)
+        inside += float(np.min(ra["F2"])) > 0.0
+    assert inside >= 3                                              # the box is crossed: the polygon product and its gradient were in play
+
+
+def test_create_accepts_four_to_eight_edges_and_nothing_else():
+    for width in (12, 15, 18, 21, 24):
+        try:
+            BatchSolver(MpcConfig(nstcobs=width)).close()
+        except MpcGpuError as e:                                  # no GPU here: the config itself passed
+            assert "no HIP device" in str(e) and "nstcobs" not in str(e), str(e)
+    for width in (13, 27, 9, 3, 0, -12):
+        with pytest.raises(MpcGpuError, match="nstcobs") as err:
+            BatchSolver(MpcConfig(nstcobs=width))
+        assert "12" in str(err.value) and "24" in str(err.value)   # the message states the accepted range
+
+
+# ---- the scenes of the GPU tests hold what those tests need (asserted there again from the same oracle values)
+@pytest.mark.parametrize("nstcobs,N", [(15, 20), (18, 20), (24, 20), (18, 12), (21, 40)])
+def test_hull_scenes_cross_polygons_in_a_quarter_and_miss_them_in_a_quarter(nstcobs, N):
+    from test_gpu_polygon_edges import cost_grad_case
+    cfg, sc, u, c, y, used = cost_grad_case(nstcobs, N)
+    S = np.array([oracle.cost_grad(oracle_cfg(cfg), u[i], sc["p"][i], float(c[i]), y[i])["F2"][-1] for i in range(len(u))])
+    assert (S > 0).mean() >= 0.25 and (S == 0).mean() >= 0.25
+    assert set(used.tolist()) == {0, 1, int(cfg.Nstcobs)}
+
+
+def test_hexagon_scene_lets_the_oracle_converge_on_half_of_the_batch():
+    from test_gpu_polygon_edges import solve_case
+    cfg, sc, verts = solve_case()
+    _, _, ro, _ = oracle.solve_batch(oracle_cfg(cfg), sc["p"])
+    assert (ro["status"] == 0).sum() >= 16

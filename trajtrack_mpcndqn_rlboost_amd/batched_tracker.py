@@ -74,8 +74,11 @@ class BatchedTracker:
         self.idx_ref[i] = 0
         self.active[i] = True
 
-    def update_static_constraints(self, i: int, obstacle_list):
-        self.stc_constraints[i] = static_obstacle_params(obstacle_list, self.config.Nstcobs, self.config.nstcobs)
+    def update_static_constraints(self, i: int, obstacle_list, pad_edges: bool = False):
+        """``pad_edges``: hulls with fewer edges than ``config.nstcobs / 3`` fill their slot with neutral half-planes
+        (``geometry.static_obstacle_params``)."""
+        self.stc_constraints[i] = static_obstacle_params(obstacle_list, self.config.Nstcobs, self.config.nstcobs,
+                                                         pad_edges=pad_edges)
 
     def update_dynamic_constraints(self, i: int, full_dyn_obstacle_list):
         """``full_dyn_obstacle_list[j][k]`` = (x, y, rx, ry, angle, alpha) of obstacle j at step k; slots beyond the

@@ -94,7 +94,8 @@ constexpr int SEGW = 9;        // LDS / workspace doubles per reference segment:
                                // bounding circle (cx, cy, R) of ALL segments from this one to the last, + 1 pad: the odd
                                // stride spreads the records of neighbouring steps over all LDS banks (an even stride
                                // gave 3-way conflicts on every segment read: -1.8 % kernel time)
-constexpr int STCW = 12;       // doubles per static obstacle    (b[4], a0[4], a1[4])
+constexpr int STCW = 12;       // doubles per static obstacle    (b[4], a0[4], a1[4]) of the kernels with a compiled horizon; the
+                               // generic-horizon kernels read the width from KParams::stcw (3 x ne, ne = 4 .. 8 edges: GENERIC POLYGONS)
 constexpr int DYNW = 9;        // workspace record per (dyn row, step): cx, cy, cosA, sinA, ihx, ihy, isx, isy, wgt
 constexpr int DYNP = 2;        // shape-constant LDS record per (row, step): cx, cy
 constexpr int DYNC = 7;        // shape-constant LDS record per row: cosA, sinA, ihx, ihy, isx, isy, alpha
@@ -157,7 +158,13 @@ struct KParams {
     // the list is taken -- the teams fill the compute units the finished wavefronts free instead of waiting for the last yield_cap
     // problems.  0 = off.
     int yield_grad;
+    // static-obstacle slot (GENERIC POLYGONS, eval_point): stcw = nstcobs doubles laid out b[ne] | a0[ne] | a1[ne] (mpc_generator.py:221-222),
+    // ne = stcw / 3 edges.  Read by the generic-horizon kernels, the compaction and the tracker's assembly; the kernels with a
+    // compiled horizon are launched for stcw = STCW only and keep the constant.
+    int stcw, ne;
 };
+// doubles per static-obstacle slot as a kernel with horizon parameter NT sees it
+template <int NT> __device__ __forceinline__ int stc_width(const KParams& kp) { return NT ? STCW : kp.stcw; }
 
 // ------------------------------------------------------------------------------------------------
 // TAIL PROMOTION (round 5).  A solve is one long dependency chain, so the last problems of a throughput launch finish on a
@@ -238,8 +245,9 @@ __host__ __device__ constexpr int even_c(int x) { return (x + 1) & ~1; }
 __host__ __device__ constexpr bool gram_shape(int N, int mem) { return MPC_LBFGS_GRAM && (N == 20 || N == 40) && mem == 10; }
 // Item-lane partials (eval_point): every item lane beyond the vector lanes parks PARTW = 5 doubles.  With a compiled horizon that
 // nearly divides the wavefront (N_hor = 20: 60 item lanes) the split is uniform and the last lanes idle -- the rule of eval_point.
-__host__ __device__ constexpr int part_doubles_c(int N, int mem) {
-    const bool compiled = (N == 20 || N == 40) && mem == 10;
+// `generic`: the shape of a compiled horizon on the generic-horizon kernel (static obstacles with more than four edges): every lane is an item lane.
+__host__ __device__ constexpr int part_doubles_c(int N, int mem, bool generic = false) {
+    const bool compiled = (N == 20 || N == 40) && mem == 10 && !generic;
     const bool uniform = compiled && (64 % N) * 5 <= N;
     const int item_lanes = uniform ? (64 / N) * N : 64;
     return (item_lanes - N) * 5;
@@ -287,7 +295,7 @@ __host__ __device__ constexpr int stash_doubles_c(int N, int mem, int minw = 3) 
     return need;
 }
 constexpr int HW_ROWS = 32;   // doubles reserved for the hinge row sums D_i; the weights W_i follow at this offset (Ndynobs <= 32)
-__host__ __device__ constexpr FixedLds fixed_lds(int N, int mem, bool lbfgs_in_lds, int minw = 3) {
+__host__ __device__ constexpr FixedLds fixed_lds(int N, int mem, bool lbfgs_in_lds, int minw = 3, bool generic = false) {
     FixedLds f{};
     int o = 0;
     f.hd = o; o += 64;
@@ -297,7 +305,7 @@ __host__ __device__ constexpr FixedLds fixed_lds(int N, int mem, bool lbfgs_in_l
     // hinge row sums + weights and the item-lane partials are never live together (LDS operations of one wavefront execute in
     // order): one region
     f.part = o; f.W = o + HW_ROWS;
-    { const int ps = part_doubles_c(N, mem); o += ps > 2 * HW_ROWS ? ps : 2 * HW_ROWS; }
+    { const int ps = part_doubles_c(N, mem, generic); o += ps > 2 * HW_ROWS ? ps : 2 * HW_ROWS; }
     f.bal = o; o += bal_doubles_c(N, mem);
     f.rho = o; o += even_c(mem);
     f.gg = o;   // Gram matrices s_i.y_j (full) + y_i.y_j (packed symmetric; square where gram_square), or the alpha scratch of the two-loop form
@@ -683,7 +691,8 @@ struct ParamVector {
     const double* p;
     __device__ __forceinline__ double operator[](int i) const { return p[i]; }
 };
-template <class Src>
+// SW: compile-time slot width of the static obstacles (the caller has a compiled horizon), 0 = KParams::stcw
+template <int SW = 0, class Src>
 __device__ __forceinline__ void prep_problem(const KParams& kp, const Src& p, double* __restrict__ ws,
                                              int* counts, int lane) {
     const int N = kp.N;
@@ -722,14 +731,15 @@ __device__ __forceinline__ void prep_problem(const KParams& kp, const Src& p, do
     // ---- static obstacles: lane o checks obstacle o
     int Ks;
     {
+        const int stcw = SW ? SW : kp.stcw;
         bool nz = false;
         if (lane < kp.Nstcobs)
-            for (int e = 0; e < STCW; ++e) nz |= (p[kp.os0 + STCW * lane + e] != 0.0);
+            for (int e = 0; e < stcw; ++e) nz |= (p[kp.os0 + stcw * lane + e] != 0.0);
         const unsigned long long m = __ballot(nz);
         Ks = __popcll(m);
         if (nz) {
             const int idx = __popcll(m & ((1ull << lane) - 1ull));
-            for (int e = 0; e < STCW; ++e) ws[kp.ws_stc + STCW * idx + e] = p[kp.os0 + STCW * lane + e];
+            for (int e = 0; e < stcw; ++e) ws[kp.ws_stc + stcw * idx + e] = p[kp.os0 + stcw * lane + e];
         }
     }
     // ---- other robots: lane j checks robot j (x,y only; theta never enters the cost)
@@ -963,7 +973,7 @@ __device__ __forceinline__ void load_problem(const KParams& kp, const double* __
     set_balanced_trips(cx, N, P::W);
     // coalesced table copies HBM -> LDS (only the active entries of this problem)
     for (int i = lane; i < N * SEGW; i += P::W) cx.seg[i] = ws[kp.ws_seg + i];
-    for (int i = lane; i < cx.Ks * STCW; i += P::W) cx.stc[i] = ws[kp.ws_stc + i];
+    for (int i = lane; i < cx.Ks * stc_width<NT>(kp); i += P::W) cx.stc[i] = ws[kp.ws_stc + i];
     for (int i = lane; i < cx.Kf * N * 2; i += P::W) cx.fxy[i] = ws[kp.ws_fxy + i];
     if (SC) {
         // shape-constant rows: per-row constants from the step-0 record (+ alpha), per-step centre, per-step q_dyn
@@ -1270,26 +1280,60 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
                 }
             }
         }
-        // static polygons, 4 half-planes each (mpc_generator.py:219-225,46-54)
-        MPC_ITEM_LOOP
-        for (int o = c_isub; o < cx.Ks; o += LPS) {
-            const double* s = cx.stc + STCW * o;
-            const double h0 = s[0] - s[4] * px - s[8] * py, h1 = s[1] - s[5] * px - s[9] * py;
-            const double h2 = s[2] - s[6] * px - s[10] * py, h3 = s[3] - s[7] * px - s[11] * py;
-            // a point outside (some half-plane value <= 0) has the product exactly 0: the squares and products are formed only in
-            // the trips in which some lane is inside a polygon
-            if (!P::any(fmin(fmin(h0, h1), fmin(h2, h3)) > 0.0)) continue;
-            const double m0 = fmax(0.0, h0), m1 = fmax(0.0, h1), m2 = fmax(0.0, h2), m3 = fmax(0.0, h3);
-            const double q0 = m0 * m0, q1 = m1 * m1, q2 = m2 * m2, q3 = m3 * m3;
-            const double p01 = q0 * q1, p23 = q2 * q3;
-            const double prod = p01 * p23;
-            if (prod > 0.0) {
-                S_l += prod;
-                if (!VO) {
-                    const double r0 = 2.0 * m0 * q1 * p23, r1 = 2.0 * m1 * q0 * p23;
-                    const double r2 = 2.0 * m2 * q3 * p01, r3 = 2.0 * m3 * q2 * p01;
-                    dsx -= r0 * s[4] + r1 * s[5] + r2 * s[6] + r3 * s[7];
-                    dsy -= r0 * s[8] + r1 * s[9] + r2 * s[10] + r3 * s[11];
+        // static polygons (mpc_generator.py:219-225,46-54): 4 half-planes each in the kernels with a compiled horizon (and in the generic
+        // ones at that width: a wave-uniform test), else the generic form over kp.ne edges -- GENERIC POLYGONS
+        if (NT != 0 || kp.ne == 4) {
+            MPC_ITEM_LOOP
+            for (int o = c_isub; o < cx.Ks; o += LPS) {
+                const double* s = cx.stc + STCW * o;
+                const double h0 = s[0] - s[4] * px - s[8] * py, h1 = s[1] - s[5] * px - s[9] * py;
+                const double h2 = s[2] - s[6] * px - s[10] * py, h3 = s[3] - s[7] * px - s[11] * py;
+                // a point outside (some half-plane value <= 0) has the product exactly 0: the squares and products are formed only in
+                // the trips in which some lane is inside a polygon
+                if (!P::any(fmin(fmin(h0, h1), fmin(h2, h3)) > 0.0)) continue;
+                const double m0 = fmax(0.0, h0), m1 = fmax(0.0, h1), m2 = fmax(0.0, h2), m3 = fmax(0.0, h3);
+                const double q0 = m0 * m0, q1 = m1 * m1, q2 = m2 * m2, q3 = m3 * m3;
+                const double p01 = q0 * q1, p23 = q2 * q3;
+                const double prod = p01 * p23;
+                if (prod > 0.0) {
+                    S_l += prod;
+                    if (!VO) {
+                        const double r0 = 2.0 * m0 * q1 * p23, r1 = 2.0 * m1 * q0 * p23;
+                        const double r2 = 2.0 * m2 * q3 * p01, r3 = 2.0 * m3 * q2 * p01;
+                        dsx -= r0 * s[4] + r1 * s[5] + r2 * s[6] + r3 * s[7];
+                        dsy -= r0 * s[8] + r1 * s[9] + r2 * s[10] + r3 * s[11];
+                    }
+                }
+            }
+        } else {
+            // GENERIC POLYGONS: slot = b[ne] | a0[ne] | a1[ne], ne = 5 .. 8 edges.  Pass 1 finds the smallest half-plane value (the
+            // same early-out as above: a trip in which no lane is inside costs ne fused multiply-adds).  Pass 2 forms
+            // prod = prod_e m_e^2 edge by edge and, with it, the derivative sum_e pre_{e-1} (2 m_e a_e) suf_{e+1} -- prefix product
+            // times suffix product, no division -- by the product rule as the loop goes: G_e = G_{e-1} q_e + pre_{e-1} 2 m_e a_e
+            // folds the suffix products in without an array of edges (a run-time index would put one into scratch memory).
+            // A neutral row (b, a0, a1) = (1, 0, 0) has m = q = 1 and a = 0: it multiplies by exactly 1 and adds exactly +-0.
+            const int ne = kp.ne, stcw = kp.stcw;
+            MPC_ITEM_LOOP
+            for (int o = c_isub; o < cx.Ks; o += LPS) {
+                const double* s = cx.stc + stcw * o;
+                double hmin = inf;
+                for (int e = 0; e < ne; ++e) hmin = fmin(hmin, s[e] - s[ne + e] * px - s[2 * ne + e] * py);
+                if (!P::any(hmin > 0.0)) continue;
+                double prod = 1.0, Gx = 0.0, Gy = 0.0;
+                for (int e = 0; e < ne; ++e) {
+                    const double a0 = s[ne + e], a1 = s[2 * ne + e];
+                    const double m = fmax(0.0, s[e] - a0 * px - a1 * py);
+                    const double q = m * m;
+                    if (!VO) {
+                        const double r = 2.0 * m * prod;
+                        Gx = Gx * q + r * a0;
+                        Gy = Gy * q + r * a1;
+                    }
+                    prod *= q;
+                }
+                if (prod > 0.0) {
+                    S_l += prod;
+                    if (!VO) { dsx -= Gx; dsy -= Gy; }
                 }
             }
         }

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
         }
     }
     // io.p == NULL: the record was already written by the tracker's assembly kernel (mpc_tracker.hpp)
-    if (wid == 0 && io.p) prep_problem(kp, ParamVector{io.p + (size_t)b * kp.np}, ws, io.counts, lane);
+    if (wid == 0 && io.p) prep_problem<NT ? STCW : 0>(kp, ParamVector{io.p + (size_t)b * kp.np}, ws, io.counts, lane);
     __syncthreads();
 
     // ---- problem context: tables shared by the four wavefronts, work areas and L-BFGS memory per wavefront
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
         set_balanced_trips(cx, N, WAVE);
         const int T = WAVE * TW;
         for (int i = threadIdx.x; i < N * SEGW; i += T) cx.seg[i] = ws[kp.ws_seg + i];
-        for (int i = threadIdx.x; i < cx.Ks * STCW; i += T) cx.stc[i] = ws[kp.ws_stc + i];
+        for (int i = threadIdx.x; i < cx.Ks * stc_width<NT>(kp); i += T) cx.stc[i] = ws[kp.ws_stc + i];
         for (int i = threadIdx.x; i < cx.Kf * N * 2; i += T) cx.fxy[i] = ws[kp.ws_fxy + i];
         for (int i = threadIdx.x; i < cx.Kd * N * DYNW; i += T) cx.dyn[i] = ws[kp.ws_dyn + i];
     }

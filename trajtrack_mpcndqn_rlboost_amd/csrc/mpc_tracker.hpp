@@ -75,7 +75,7 @@ __global__ __launch_bounds__(WAVE) void tracker_assemble_kernel(KParams kp, Trac
     }
     TrackerParams p;
     p.state = st; p.last_u = t.last_actions + 2 * b; p.refs = refs + (size_t)b * N * 3;
-    p.stc = t.stc + (size_t)b * kp.Nstcobs * STCW; p.dyn = t.dyn + (size_t)b * kp.Ndynobs * 6 * N;
+    p.stc = t.stc + (size_t)b * kp.Nstcobs * kp.stcw; p.dyn = t.dyn + (size_t)b * kp.Ndynobs * 6 * N;
     p.other = t.other ? t.other + (size_t)b * 3 * N * kp.Nother : nullptr;
     p.tuning = t.tuning;
     // speed reference: constant, scaled down near the FINAL goal, floored by low_speed (trajectory_generator.py:257-264)

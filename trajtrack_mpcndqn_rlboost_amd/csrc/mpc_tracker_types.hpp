@@ -15,7 +15,7 @@ struct TrackerView {
     const double* ref;           // [B][ref_cap][3] global reference trajectories, padded
     const int32_t* ref_len;      // [B]
     int32_t* idx_ref;            // [B]     in/out
-    const double* stc;           // [B][Nstcobs * 12]
+    const double* stc;           // [B][Nstcobs * nstcobs]
     const double* dyn;           // [B][Ndynobs * 6 * N]
     const double* other;         // [B][3 * N * Nother] or NULL (zeros)
     double* pred_states;         // [B][N][3]  out

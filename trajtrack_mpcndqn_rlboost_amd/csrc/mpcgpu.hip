@@ -181,7 +181,10 @@ inline bool stream_is_capturing(hipStream_t s) {
 // The choice never depends on the batch: results must not change with the batch a problem travels in.
 // The kernels with a compile-time horizon (N_hor = 20, 40: the reference's yaml files) also fix the L-BFGS memory at the
 // reference's 10 (mpc_kernels.hpp MemOf); every other configuration runs the generic kernel.
-inline int compiled_horizon(const Handle* h) { return (h->kp.N == 20 || h->kp.N == 40) && h->kp.mem == 10 ? h->kp.N : 0; }
+// They are also written for static obstacles of four edges (STCW doubles per slot): any other accepted nstcobs runs the generic
+// kernel, whose polygon term loops over the edges (mpc_kernels.hpp GENERIC POLYGONS) -- and with it neither two problems per
+// wavefront nor the balanced pair of N_hor = 40 is on offer.
+inline int compiled_horizon(const Handle* h) { return (h->kp.N == 20 || h->kp.N == 40) && h->kp.mem == 10 && h->kp.stcw == STCW ? h->kp.N : 0; }
 inline bool duo_available(const Handle* h) { return compiled_horizon(h) == 20; }
 inline bool use_duo(const Handle* h) { return duo_available(h) && h->pairing == 1; }
 
@@ -205,6 +208,7 @@ void fill_static_params(Handle* h) {
     const int N = c.N;
     k.N = N;
     k.Nother = c.Nother; k.Nstcobs = c.Nstcobs; k.Ndynobs = c.Ndynobs; k.mem = c.lbfgs_mem;
+    k.stcw = c.nstcobs; k.ne = c.nstcobs / 3;
     k.max_inner = c.max_inner; k.max_outer = c.max_outer;
     k.ls_fallback = 0;
     k.stall_rule = 0;
@@ -227,7 +231,7 @@ void fill_static_params(Handle* h) {
     int o = HDR;
     k.ws_vref = o; o += even(N);
     k.ws_seg = o; o += even(N * SEGW);
-    k.ws_stc = o; o += c.Nstcobs * STCW;
+    k.ws_stc = o; o += even(c.Nstcobs * k.stcw);
     k.ws_fxy = o; o += c.Nother * N * 2;
     k.ws_dyn = o; o += even(c.Ndynobs * N * DYNW);
     k.ws_qd = o; o += even(N);
@@ -245,7 +249,7 @@ void fill_static_params(Handle* h) {
 }
 
 // sizes of the fixed regions: mpc_kernels.hpp (part_doubles_c, stash_doubles_c, fixed_lds) -- shared with the kernels
-int part_doubles(const KParams& k) { return part_doubles_c(k.N, k.mem); }
+int part_doubles(const KParams& k) { return part_doubles_c(k.N, k.mem, k.stcw != STCW); }
 bool gram_layout(const KParams& k) { return gram_shape(k.N, k.mem); }
 int stash_doubles(const KParams& k, int minw = 3) { return stash_doubles_c(k.N, k.mem, minw); }
 
@@ -258,13 +262,13 @@ void fill_lds_layout(KParams& k, int mKs, int mKf, int mKd, bool shape_const, bo
     const int N = k.N;
     k.mKs = mKs; k.mKf = mKf; k.mKd = mKd;
     // fixed part first (compile-time offsets in the kernels with a compiled horizon), then the tables that follow the batch
-    const FixedLds f = fixed_lds(N, k.mem, lbfgs_in_lds, minw);
+    const FixedLds f = fixed_lds(N, k.mem, lbfgs_in_lds, minw, k.stcw != STCW);
     k.l_hd = f.hd; k.l_seg = f.seg; k.l_pos = f.pos; k.l_stash = f.stash;
     k.l_H = f.part; k.l_W = f.W; k.l_part = f.part; k.l_bal = f.bal;
     k.l_rho = f.rho; k.l_alpha = f.gg; k.l_gg = f.gg;
     k.l_S = f.S; k.l_Y = f.Y; k.l_old = f.old;
     int o = f.end;
-    k.l_stc = o; o += mKs * STCW;
+    k.l_stc = o; o += even(mKs * k.stcw);
     k.l_fxy = o; o += mKf * N * 2;
     k.l_dynl = 0;
     if (shape_const && linear) {
@@ -293,7 +297,7 @@ void fill_team_layout(KParams& k, int tw, int mKs, int mKf, int mKd) {
     k.mKs = mKs; k.mKf = mKf; k.mKd = mKd;
     int o = 0;
     k.l_seg = o; o += even(N * SEGW);
-    k.l_stc = o; o += k.mKs * STCW;
+    k.l_stc = o; o += even(k.mKs * k.stcw);
     k.l_fxy = o; o += k.mKf * N * 2;
     k.l_dyn = o; o += even(k.mKd * N * DYNW);
     k.l_dync = k.l_dyn; k.l_qd = k.l_dyn;
@@ -380,7 +384,8 @@ int validate(const mpcgpu_config* c) {
     if (!c) return fail(nullptr, -1, "config is NULL");
     if (c->N < 2 || c->N > 64) return fail(nullptr, -1, "N_hor=%d unsupported (2..64)", c->N);
     if (c->nu != 2 || c->ns != 3) return fail(nullptr, -1, "only the unicycle model (nu=2, ns=3) is supported, got nu=%d ns=%d", c->nu, c->ns);
-    if (c->nstcobs != 12) return fail(nullptr, -1, "nstcobs=%d unsupported (12 = 4 edges x (b,a0,a1))", c->nstcobs);
+    if (c->nstcobs < 3 * MPCGPU_MIN_EDGES || c->nstcobs > 3 * MPCGPU_MAX_EDGES || c->nstcobs % 3 != 0)
+        return fail(nullptr, -1, "nstcobs=%d unsupported (12, 15, 18, 21 or 24 = 4 .. 8 edges x (b,a0,a1))", c->nstcobs);
     if (c->ndynobs != 6) return fail(nullptr, -1, "ndynobs=%d unsupported (6)", c->ndynobs);
     if (c->Nother < 0 || c->Nother > 16) return fail(nullptr, -1, "Nother=%d unsupported (0..16)", c->Nother);
     if (c->Nstcobs < 0 || c->Nstcobs > 16) return fail(nullptr, -1, "Nstcobs=%d unsupported (0..16)", c->Nstcobs);

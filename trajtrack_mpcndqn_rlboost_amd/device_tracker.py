@@ -80,8 +80,10 @@ class DeviceTracker:
         self._h_ref[i] = global_reference_trajectory(self.config.ts, ref_path_list, self._h_states[i], base_speed)
         self._init_rows.add(int(i))
 
-    def update_static_constraints(self, i: int, obstacle_list):
-        self._h_stc[i] = static_obstacle_params(obstacle_list, self.config.Nstcobs, self.config.nstcobs)
+    def update_static_constraints(self, i: int, obstacle_list, pad_edges: bool = False):
+        """``pad_edges``: as ``BatchedTracker.update_static_constraints``."""
+        self._h_stc[i] = static_obstacle_params(obstacle_list, self.config.Nstcobs, self.config.nstcobs,
+                                                pad_edges=pad_edges)
         self._stc_rows.add(int(i))
 
     def _upload(self):

@@ -26,17 +26,30 @@ def polygon_halfspace_representation(polygon_points: np.ndarray) -> Tuple[List[f
     return b.tolist(), a[:, 0].tolist(), a[:, 1].tolist()
 
 
+NEUTRAL_HALFPLANE = (1.0, 0.0, 0.0)   # (b, a0, a1): max(0, 1 - 0 x - 0 y) = 1 everywhere
+
+
 def static_obstacle_params(obstacle_list: Sequence[Sequence[Sequence[float]]], n_slots: int,
-                           n_per_obstacle: int = 12) -> List[float]:
+                           n_per_obstacle: int = 12, pad_edges: bool = False) -> List[float]:
     """Padded static-obstacle block (``src/interface_mpc.py:23,60-63``).  Unlike the reference, an obstacle whose
     hull does not have exactly ``n_per_obstacle / 3`` edges is an error instead of silently changing the length of
-    the block."""
+    the block.
+
+    ``pad_edges``: a hull with FEWER edges fills its slot with neutral half-planes ``(b, a0, a1) = (1, 0, 0)``.  Such a
+    row has the value 1 at every point: it multiplies the product of squared hinges
+    (``mpc_generator.py:46-54``) by exactly 1 and adds exactly zero to its gradient, so the padded polygon IS the
+    smaller one -- a triangle in a solver built for four edges, quads and hexagons side by side in one built for six.
+    A hull with more edges than the slot has is an error in either mode."""
     if len(obstacle_list) > n_slots:
         raise ValueError(f"{len(obstacle_list)} static obstacles but only {n_slots} slots")
     block = [0.0] * (n_slots * n_per_obstacle)
     for i, poly in enumerate(obstacle_list):
         b, a0, a1 = polygon_halfspace_representation(np.array(poly, dtype=float))
-        if 3 * len(b) != n_per_obstacle:
-            raise ValueError(f"static obstacle {i} has {len(b)} hull edges; the solver is built for {n_per_obstacle // 3}")
+        ne = n_per_obstacle // 3
+        if len(b) != ne and not (pad_edges and len(b) < ne):
+            raise ValueError(f"static obstacle {i} has {len(b)} hull edges; the solver is built for {ne}"
+                             + (" or fewer" if pad_edges else ""))
+        fill = ne - len(b)
+        b, a0, a1 = b + [NEUTRAL_HALFPLANE[0]] * fill, a0 + [NEUTRAL_HALFPLANE[1]] * fill, a1 + [NEUTRAL_HALFPLANE[2]] * fill
         block[i * n_per_obstacle:(i + 1) * n_per_obstacle] = b + a0 + a1
     return block

@@ -83,11 +83,13 @@ class InterfaceMpc:
         self._traj_gen.set_work_mode(mode)
         self._traj_gen.set_ref_trajectory(self._ref_path)
 
-    def update_static_constraints(self, obstacle_list) -> None:
+    def update_static_constraints(self, obstacle_list, pad_edges: bool = False) -> None:
         """Polygons (vertex lists) -> half-space rows in the first ``len(obstacle_list)`` slots; later slots keep
-        whatever they held (the reference overwrites slot by slot, ``interface_mpc.py:60-63``)."""
+        whatever they held (the reference overwrites slot by slot, ``interface_mpc.py:60-63``).  ``pad_edges``: hulls
+        with fewer edges than ``config.nstcobs / 3`` fill their slot with neutral half-planes
+        (``geometry.static_obstacle_params``)."""
         cfg = self.config
-        rows = static_obstacle_params(obstacle_list, cfg.Nstcobs, cfg.nstcobs)
+        rows = static_obstacle_params(obstacle_list, cfg.Nstcobs, cfg.nstcobs, pad_edges=pad_edges)
         used = len(obstacle_list) * cfg.nstcobs
         self._stc[:used] = rows[:used]
 

@@ -34,6 +34,43 @@ def rect_halfspaces(x0, x1, y0, y1):
     return np.concatenate([b, a0, a1], axis=-1)
 
 
+def pad_halfspaces(rows: np.ndarray, n_edges: int) -> np.ndarray:
+    """Slots ``[..., 3 m] = b[m] + a0[m] + a1[m]`` widened to ``n_edges >= m`` edges with neutral half-planes
+    ``(b, a0, a1) = (1, 0, 0)``: a row that is 1 everywhere multiplies the polygon product by exactly 1
+    (``geometry.static_obstacle_params``, ``pad_edges``).  ``n_edges == m`` returns the rows as they are."""
+    rows = np.asarray(rows, dtype=float)
+    m = rows.shape[-1] // 3
+    if n_edges < m:
+        raise ValueError(f"a polygon with {m} edges does not fit a slot of {n_edges}")
+    if n_edges == m:
+        return rows
+    out = np.zeros(rows.shape[:-1] + (3 * n_edges,))
+    out[..., :n_edges] = 1.0
+    for part in range(3):
+        out[..., part * n_edges: part * n_edges + m] = rows[..., part * m:(part + 1) * m]
+    return out
+
+
+def polygon_halfspaces(vertices, n_edges: int) -> np.ndarray:
+    """(b, a0, a1) of convex polygons given by their vertices in order (either orientation), ``[..., nv, 2]``, normalised
+    like the reference's facet enumeration (``src/util/utils_geo.py:33-59``: a . (v - centre) = 1 on every facet,
+    b = a . centre + 1, centre = mean of the vertices) and padded to ``n_edges`` edges (``pad_halfspaces``).
+    Edge e runs from vertex e to vertex e + 1.  Output ``[..., 3 n_edges]``."""
+    v = np.asarray(vertices, dtype=float)
+    nv = v.shape[-2]
+    if nv < 3:
+        raise ValueError("a polygon needs three vertices")
+    if nv > n_edges:
+        raise ValueError(f"a polygon with {nv} edges does not fit a slot of {n_edges}")
+    c = v.mean(axis=-2, keepdims=True)
+    d = np.roll(v, -1, axis=-2) - v
+    n = np.stack([d[..., 1], -d[..., 0]], axis=-1)               # a normal of every edge; its sign cancels below
+    s = np.sum(n * (v - c), axis=-1, keepdims=True)              # n . (vertex - centre)
+    a = n / s
+    b = np.sum(a * c, axis=-1) + 1.0
+    return pad_halfspaces(np.concatenate([b, a[..., 0], a[..., 1]], axis=-1), n_edges)
+
+
 def work_mode_weights(cfg: MpcConfig) -> np.ndarray:
     """tuning_params of every non-'aligning' mode (trajectory_generator.py:129-130)."""
     return np.array([cfg.qpos, cfg.qvel, cfg.qtheta, cfg.lin_vel_penalty, cfg.ang_vel_penalty,
@@ -133,12 +170,14 @@ def make_batch(cfg: MpcConfig, B: int, n_dyn: int = 8, seed: int = 1234, n_other
         blk[:, :, 1] = cy[:, None] + vy[:, None] * (ks - k0[:, None])
         p[:, off["c"] + j * 3 * N: off["c"] + (j + 1) * 3 * N] = blk.reshape(B, 3 * N)
 
-    # ---- static obstacles: corridor walls + one box ahead on the path, inflated
+    # ---- static obstacles: corridor walls + one box ahead on the path, inflated; quads in slots of cfg.nstcobs / 3 edges (the
+    #      same families at every accepted width: the feasible set does not change with the neutral rows)
     o = 0
+    sw = int(cfg.nstcobs)
     if with_walls:
         for (wx, wy) in WALLS:
-            p[:, off["os"] + 12 * o: off["os"] + 12 * (o + 1)] = rect_halfspaces(
-                wx[0] - INFLATE, wx[1] + INFLATE, wy[0] - INFLATE, wy[1] + INFLATE)
+            p[:, off["os"] + sw * o: off["os"] + sw * (o + 1)] = pad_halfspaces(rect_halfspaces(
+                wx[0] - INFLATE, wx[1] + INFLATE, wy[0] - INFLATE, wy[1] + INFLATE), sw // 3)
             o += 1
     if with_box:
         kb = rng.integers(min(12, N - 1), min(18, N - 1) + 1, B)   # 3.1 .. 4.6 m ahead
@@ -162,7 +201,8 @@ def make_batch(cfg: MpcConfig, B: int, n_dyn: int = 8, seed: int = 1234, n_other
             lat = side * (np.hypot(hx, hy) + box_clearance)
             bx = ref[np.arange(B), kb, 0] - lat * np.sin(ref[np.arange(B), kb, 2])
             by = ref[np.arange(B), kb, 1] + lat * np.cos(ref[np.arange(B), kb, 2])
-        p[:, off["os"] + 12 * o: off["os"] + 12 * (o + 1)] = rect_halfspaces(bx - hx, bx + hx, by - hy, by + hy)
+        p[:, off["os"] + sw * o: off["os"] + sw * (o + 1)] = pad_halfspaces(
+            rect_halfspaces(bx - hx, bx + hx, by - hy, by + hy), sw // 3)
         o += 1
 
     # ---- dynamic discs crossing the neighbourhood of the path within the horizon
