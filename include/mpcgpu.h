@@ -201,7 +201,10 @@ int32_t mpcgpu_reserve_batch(void* handle, int32_t B);
  *       -1 (default) automatic: the faster layout as measured on the MI355X -- today one problem per wavefront for every
  *                    horizon
  *        0           one problem per wavefront (the layout BASELINE.json's north_star words)
- *        1           two problems per wavefront (rows 0-1 / rows 2-3; compiled for N_hor = 20, error for other horizons)
+ *        1           two problems per wavefront (rows 0-1 / rows 2-3; compiled for N_hor = 20, error for other horizons).
+ *                    With static obstacles of more than four edges (nstcobs > 12) N_hor = 20 runs the generic kernels, which
+ *                    have one layout: the request is accepted and one problem per wavefront runs
+ *                    (mpcgpu_last_problems_per_wavefront reports it).
  *     The choice never depends on the batch.  Both layouts run the same source (csrc/mpc_kernels.hpp, lane models Solo / Duo);
  *     their results differ by floating-point summation order only.
  *   MPCGPU_OPT_TEAM_BATCH  largest batch that is solved by the LATENCY kernel (csrc/mpc_team.hpp: one problem per workgroup of

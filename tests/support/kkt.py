@@ -59,13 +59,14 @@ def hard_constraints(cfg, p, u, with_parts=False):
                  - (ex * np.sin(ang) - ey * np.cos(ang)) ** 2 / (ry + 1e-6) ** 2
         ih_rows.append(ih)
         g.append(ih)
-    stc = p[off["os"]:off["od"]].reshape(cfg.Nstcobs, 12)
+    ne = int(cfg.nstcobs) // 3                                                   # edges per slot: b[ne] | a0[ne] | a1[ne]
+    stc = p[off["os"]:off["od"]].reshape(cfg.Nstcobs, 3 * ne)
     S = 0.0
     for o in range(cfg.Nstcobs):
         if not np.any(stc[o]):
             continue
-        b, a0, a1 = stc[o, 0:4], stc[o, 4:8], stc[o, 8:12]
-        h = b[None, :] - X[:, 0:1] * a0[None, :] - X[:, 1:2] * a1[None, :]      # [N, 4]
+        b, a0, a1 = stc[o, 0:ne], stc[o, ne:2 * ne], stc[o, 2 * ne:3 * ne]
+        h = b[None, :] - X[:, 0:1] * a0[None, :] - X[:, 1:2] * a1[None, :]      # [N, ne]
         g.append(h.min(axis=1))
         S += float(np.prod(np.maximum(h, 0.0) ** 2, axis=1).sum())
     gv = np.concatenate(g) if g else np.zeros(0)

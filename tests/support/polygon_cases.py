@@ -94,3 +94,43 @@ def smallest_halfplane_value(rows, ne, pts):
     """min_e (b_e - a0_e x - a1_e y) of one slot at points [..., 2]: > 0 exactly inside the polygon."""
     b, a0, a1 = rows[:ne], rows[ne:2 * ne], rows[2 * ne:3 * ne]
     return np.min(b - a0 * pts[..., 0:1] - a1 * pts[..., 1:2], axis=-1)
+
+
+# ---- the reference's vectors with 5 .. 8 edges (tests/golden/costgrad_polygons.npz, make_polygon_fixtures.py)
+_golden = {}
+
+
+def golden():
+    if not _golden:
+        import os
+        with np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "golden", "costgrad_polygons.npz")) as fx:
+            _golden.update({k: fx[k] for k in fx.files})
+    return _golden
+
+
+def golden_groups():
+    fx = golden()
+    return sorted({(int(w), int(N)) for w, N in zip(fx["nstcobs"], fx["N"])})
+
+
+def golden_batch(cfg, select=None):
+    """the cases of cfg's (nstcobs, N_hor), unpadded, as a batch of tests/support/cost_forms.py; `select(p)` filters them"""
+    fx = golden()
+    N, n_p = int(cfg.N_hor), int(cfg.num_params)
+    sel = np.nonzero((fx["nstcobs"] == int(cfg.nstcobs)) & (fx["N"] == N))[0]
+    if select is not None:
+        sel = np.array([i for i in sel if select(fx["p"][i, :n_p])], dtype=int)
+    n = 2 * N
+    return dict(idx=sel, tag=fx["tag"][sel], family=fx["family"][sel], u=fx["u"][sel, :n], p=fx["p"][sel, :n_p], c=fx["c"][sel],
+                y=fx["y"][sel, :n], f=fx["f"][sel], psi=fx["psi"][sel], grad_psi=fx["grad_psi"][sel, :n],
+                grad_f=fx["grad_f"][sel, :n], F1=fx["F1"][sel, :n], F2=fx["F2"][sel])
+
+
+def halfplane_values(cfg, p, u):
+    """b - a0 x - a1 y of every (step, slot in use, edge) of one problem, [N, slots, ne]; a slot is in use when any entry is non-zero"""
+    ne = int(cfg.nstcobs) // 3
+    off = cfg.offsets()
+    slots = p[off["os"]:off["od"]].reshape(int(cfg.Nstcobs), 3, ne)
+    slots = slots[np.any(slots != 0.0, axis=(1, 2))]
+    pos = rollout(p[None, 0:3], u[None], cfg.ts)[0]
+    return slots[None, :, 0, :] - slots[None, :, 1, :] * pos[:, None, 0:1] - slots[None, :, 2, :] * pos[:, None, 1:2]

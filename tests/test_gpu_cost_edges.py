@@ -17,18 +17,12 @@ import pytest
 
 from conftest import load_golden, make_cfg
 from trajtrack_mpcndqn_rlboost_amd import BatchSolver
-from support.edge_cases import KINDS, dyn_rows, table_kind
+from support.cost_forms import assert_form as _assert_form, check as _check, spoiler as _spoiler
+from support.edge_cases import KINDS, table_kind
 from trajtrack_mpcndqn_rlboost_amd.solver import variant_path
 
 pytestmark = pytest.mark.gpu
-RTOL_COST = 1e-11
 FAMILIES = ["A", "B", "C", "D", "E", "F"]
-
-
-def _rel(a, b):
-    a, b = np.atleast_2d(np.asarray(a, float)), np.atleast_2d(np.asarray(b, float))
-    scale = np.maximum(1.0, np.max(np.abs(b), axis=-1, keepdims=True))
-    return np.max(np.abs(a - b) / scale, axis=-1)
 
 
 def _batch(family, N, kind=None):
@@ -50,24 +44,6 @@ def _groups():
     return sorted({(str(f), int(N)) for f, N in zip(fx["family"], fx["N"])})
 
 
-def _spoiler(cfg, b, kind):
-    """one extra problem: a copy of the first case with its last dynamic row replaced by a row 1 km away that is rotated
-    ('rot') or changes its shape with the step ('var')"""
-    p = b["p"][0].copy()
-    rows = dyn_rows(cfg, p)                         # a view into p
-    for k in range(cfg.N_hor):
-        rows[-1, k] = [1e3, 1e3, 0.5 + (0.01 * k if kind == "var" else 0.0), 0.4, 0.3, 1.0]
-    out = dict(b)
-    for key, extra in (("u", b["u"][0]), ("p", p), ("c", b["c"][0]), ("y", b["y"][0])):
-        out[key] = np.concatenate([b[key], np.asarray(extra)[None] if np.ndim(extra) else np.array([extra])])
-    return out
-
-
-def _assert_form(bs, kind):
-    s = bs.last_shape()
-    assert s["shape_const"] == (kind != "var") and s["axis_aligned"] == (kind == "axis"), (kind, s)
-
-
 def _every_form(bs, cfg, family, kind, what):
     """the cases of one table kind in their own form, then with a spoiler in each more general one; returns how many"""
     b = _batch(family, cfg.N_hor, kind)
@@ -79,19 +55,6 @@ def _every_form(bs, cfg, family, kind, what):
         _check(bs, _spoiler(cfg, b, more), f"{what} {kind} cases + {more} spoiler")
         _assert_form(bs, more)
     return len(b["idx"])
-
-
-def _check(bs, b, what):
-    """cost_grad of batch b (its first len(b['idx']) problems are checked) against the reference at RTOL_COST"""
-    m = len(b["idx"])
-    r = bs.cost_grad(b["u"], b["p"], b["c"], b["y"])
-    r0 = bs.cost_grad(b["u"], b["p"])                       # c = 0: psi is f, the gradient is grad f
-    errs = dict(f=_rel(r["f"][:m, None], b["f"][:, None]), psi=_rel(r["psi"][:m, None], b["psi"][:, None]),
-                grad=_rel(r["grad"][:m], b["grad_psi"]), F1=_rel(r["F1"][:m], b["F1"]), F2=_rel(r["F2"][:m], b["F2"]),
-                grad_f=_rel(r0["grad"][:m], b["grad_f"]), psi0=_rel(r0["psi"][:m, None], b["f"][:, None]))
-    bad = sorted({int(i) for e in errs.values() for i in np.nonzero(~(e < RTOL_COST))[0]})
-    assert not bad, f"{what}: " + "; ".join(
-        f"{b['tag'][i]}: " + ", ".join(f"{k} {v[i]:.1e}" for k, v in errs.items() if not v[i] < RTOL_COST) for i in bad)
 
 
 @pytest.mark.parametrize("family,N", _groups())

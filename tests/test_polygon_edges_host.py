@@ -1,8 +1,9 @@
 """CPU: static obstacles with 4 .. 8 edges (yaml key nstcobs = 12 .. 24) -- the oracle's generic polygon branch against an
 independent restatement, the host feeders with their neutral padding rows, and which configs mpcgpu_create accepts.
 
-Only four edges are pinned by reference fixtures (tests/golden/costgrad_*.npz), so the generic loop of oracle/mpc_oracle.c:185-203
--- the yardstick of tests/test_gpu_polygon_edges.py -- is held here against mpc_generator.py:46-54,219-225 restated in numpy."""
+The generic loop of oracle/mpc_oracle.c:185-203 -- the yardstick of tests/test_gpu_polygon_edges.py -- is pinned to the reference's
+own vectors with 5 .. 8 edges in tests/test_oracle_polygon_golden.py (tests/golden/costgrad_polygons.npz); here it is held,
+independently, against mpc_generator.py:46-54,219-225 restated in numpy and against central differences."""
 import numpy as np
 import pytest
 
@@ -230,3 +231,15 @@ def test_hexagon_scene_lets_the_oracle_converge_on_half_of_the_batch():
     cfg, sc, verts = solve_case()
     _, _, ro, _ = oracle.solve_batch(oracle_cfg(cfg), sc["p"])
     assert (ro["status"] == 0).sum() >= 16
+
+
+def test_heptagon_scene_at_forty_steps_lets_the_oracle_converge_on_half_of_the_batch():
+    from test_gpu_polygon_golden import solve_case_40
+    cfg, sc, verts = solve_case_40()
+    assert cfg.N_hor == 40 and cfg.nstcobs == 24 and cfg.solver_lbfgs_memory == 10       # the shape of the compiled N_hor = 40 kernels
+    _, _, ro, _ = oracle.solve_batch(oracle_cfg(cfg), sc["p"])
+    assert (ro["status"] == 0).sum() >= 16
+    off = cfg.offsets()
+    crossing = sum(polygon_cases.smallest_halfplane_value(sc["p"][i, off["os"]:off["os"] + 24], 8, sc["ref"][i, :, :2]).max() > 1e-3
+                   for i in range(len(verts)))
+    assert crossing >= len(verts) // 8                              # the heptagon covers the reference path of some problems

@@ -39,6 +39,24 @@ def test_oracle_converged_solutions_are_local_minima_of_the_reference_problem(N,
         assert_kkt(kkt.check_solution(cfg, ocfg, sc["p"][i], u[i], y[i]), f"N={N} problem {i}")
 
 
+def test_oracle_converged_solutions_beside_a_hexagon_are_local_minima_of_the_reference_problem():
+    """Static obstacles of six edges (nstcobs = 18): the hard constraint of a polygon is the smallest of six half-plane values
+    (kkt.hard_constraints reads the slot width from the config).  CPU twin of the GPU test of the same name in
+    tests/test_gpu_polygon_golden.py: every converged problem of the hexagon scene."""
+    from test_gpu_polygon_edges import solve_case
+    cfg, sc, verts = solve_case()
+    ocfg = oracle_cfg(cfg)
+    u, y, res, _ = oracle.solve_batch(ocfg, sc["p"])
+    conv = np.where(res["status"] == 0)[0]
+    assert len(conv) >= len(verts) // 2, len(conv)
+    nearest = -np.inf
+    for i in conv:
+        r = kkt.check_solution(cfg, ocfg, sc["p"][i], u[i], y[i])
+        assert_kkt(r, f"hexagon problem {i}")
+        nearest = max(nearest, r["g_static_max"])
+    assert nearest > -0.1                                     # some converged plan passes the hexagon within a tenth (half-plane units)
+
+
 def test_an_active_hard_constraint_gets_a_non_negative_multiplier():
     """One disc, no box: some converged plans touch the disc's hard ellipse; the Lagrangian residual then needs mu > 0."""
     cfg = make_cfg(20, **GROWING_PENALTY)

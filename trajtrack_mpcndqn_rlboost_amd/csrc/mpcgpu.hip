@@ -1346,7 +1346,10 @@ int32_t mpcgpu_set_option(void* handle, int32_t option, double value) {
             return 0;
         case MPCGPU_OPT_PAIRING:
             if (value != -1.0 && value != 0.0 && value != 1.0) return fail(h, -1, "pairing must be -1 (automatic), 0 or 1, got %g", value);
-            if (value == 1.0 && !duo_available(h)) return fail(h, -1, "two problems per wavefront are compiled for N_hor = 20 only (N_hor = %d)", h->kp.N);
+            // N_hor = 20 with wider static slots runs the generic kernels (compiled_horizon), which have no such layout: the request
+            // stands, use_duo() answers no and one problem per wavefront runs -- the same handle code serves every accepted nstcobs
+            if (value == 1.0 && !duo_available(h) && !(h->kp.N == 20 && h->kp.mem == 10 && h->kp.stcw != STCW))
+                return fail(h, -1, "two problems per wavefront are compiled for N_hor = 20 only (N_hor = %d)", h->kp.N);
             h->pairing = (int)value;
             return 0;
         case MPCGPU_OPT_LINEAR_TABLES:
