@@ -72,6 +72,33 @@ int32_t mpcgpu_env_step_fresh_dev(int32_t device, const mpcgpu_env_params* param
                                   uint8_t* terminated, uint8_t* truncated, float* terminal_obs_internal,
                                   float* terminal_obs_external, int32_t max_episode_steps, void* stream);
 
+/*
+ * The same step for the image observation (mpcgpu_env_step_imgs_autoreset_dev with map turnover): img, img_state,
+ * distance_field and the images as in mpcgpu_env.h, the tables as above.  Two launches on `stream`, the step and then the
+ * image kernel.  Which record an image is drawn from, for a row whose episode ended in this step:
+ *     terminal_obs_image[b]  the record the episode ENDED on -- its outlines and key frames at the clock of the last step,
+ *                            with the image history up to it -- also when the row has moved to its spare in this call
+ *     obs_image[b]           the record the row is on NOW, records2[which[b]][b] as the step left which[b]: the first
+ *                            image of the next episode, on the new map when the row turned over
+ * and for every other row obs_image[b] from records2[which[b]][b].  The step leaves the table index a row was on at its
+ * entry in img_state[b][13] for the image kernel; img_state[b][8..13] are scratch between the two launches.
+ * max_episode_steps = 0: no reset and no turnover, as mpcgpu_env_step_imgs_dev on records2[which[b]][b] (action may be
+ * NULL; truncated and terminal_obs_* are not written).
+ * Ordering: stream order only.  Whatever refills spares is enqueued BEHIND this call on the same stream; it may then
+ * overwrite the record a row has just left (that slot is the row's new spare), because the image kernel that drew the
+ * terminal image from it has finished by then.  A writer on another stream must be ordered behind the image kernel.
+ * Refused before anything is enqueued (< 0, text via mpcgpu_env_last_error): a null which / spare_ready / loaded / stale /
+ * img_state / distance_field / obs_image, a negative max_episode_steps, auto-reset without action or truncated, invalid
+ * image params, and an n_edge_max whose edge staging does not fit the image kernel's LDS.
+ */
+int32_t mpcgpu_env_step_imgs_fresh_dev(int32_t device, const mpcgpu_env_params* params, const mpcgpu_env_img_params* img,
+                                       int32_t B, const double* records2, int32_t* which, int32_t* spare_ready,
+                                       int32_t* loaded, int32_t* stale, double* state, double* img_state,
+                                       const uint8_t* distance_field, const int32_t* action, float* obs_internal,
+                                       uint8_t* obs_image, double* reward, uint8_t* terminated, uint8_t* truncated,
+                                       float* terminal_obs_internal, uint8_t* terminal_obs_image,
+                                       int32_t max_episode_steps, void* stream);
+
 /* doubles of one spec record (MPCGPU_MAP_SPEC_DOUBLES; no device needed) */
 int32_t mpcgpu_map_spec_doubles(void);
 

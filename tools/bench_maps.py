@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Secondary benchmark: the device-resident map stream.
 
-    python tools/bench_maps.py [--batch B] [--steps K] [--warmup W] [--cpu-maps N] [--run-steps S] [--refill-every R ...]
+    python tools/bench_maps.py [--variant rays|imgs] [--batch B] [--steps K] [--warmup W] [--cpu-maps N] [--run-steps S]
+                               [--refill-every R ...]
+
+``--variant imgs`` runs the same legs on the image environment (BatchedImgsEnv(map_turnover=True): two launches per step).
 
 Prints ONE JSON line per measurement in the shape of tools/bench_plan.py's (metric / value / config / cpu_baseline):
 
@@ -54,8 +57,12 @@ def start_maps(n):
     return [maps[i % len(maps)] for i in range(n)]
 
 
-def make_env(B, refill_every, max_episode_steps=400):
-    env = rl_env.BatchedRaysEnv(start_maps(B), max_episode_steps=max_episode_steps, capacity=map_stream.DYNAMIC_CAPACITY)
+def make_env(B, refill_every, max_episode_steps=400, variant="rays"):
+    if variant == "imgs":
+        env = rl_env.BatchedImgsEnv(start_maps(B), max_episode_steps=max_episode_steps, capacity=map_stream.DYNAMIC_CAPACITY,
+                                    map_turnover=True)
+    else:
+        env = rl_env.BatchedRaysEnv(start_maps(B), max_episode_steps=max_episode_steps, capacity=map_stream.DYNAMIC_CAPACITY)
     env.enable_fresh_maps(seed=0, refill_every=refill_every)
     env.reset()
     return env
@@ -63,6 +70,7 @@ def make_env(B, refill_every, max_episode_steps=400):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--variant", choices=["rays", "imgs"], default="rays")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -71,7 +79,7 @@ def main():
     ap.add_argument("--refill-every", type=int, nargs="*", default=[1, 4, 8, 16, 32])
     args = ap.parse_args()
     B = args.batch
-    env = make_env(B, 10 ** 9)
+    env = make_env(B, 10 ** 9, variant=args.variant)
 
     def empty():
         env.spare_ready.zero_()
@@ -82,7 +90,7 @@ def main():
             "unit": "maps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * refill_s,
             "higher_is_better": True, "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"{B} generate_map_dynamic maps per refill, one wavefront per map and kernel",
-                       "batch_per_gpu": B, "record_bytes": env.records.shape[1] * 8, "status_counts_from_minus_1": status}}
+                       "variant": args.variant, "batch_per_gpu": B, "record_bytes": env.records.shape[1] * 8, "status_counts_from_minus_1": status}}
     if args.cpu_maps > 0:
         specs = [map_stream.spec_of(0, b) for b in range(args.cpu_maps)]
         paths, st = path_plan.plan_reference_paths(specs)
@@ -98,11 +106,12 @@ def main():
 
     acts = torch.randint(0, 9, (B,), device=env.device, dtype=torch.int32)
     step_s = time_launches(lambda: env._fresh_launch(acts, env.max_episode_steps), args.steps, args.warmup)
-    print(json.dumps({"metric": "one refill of B spares vs one fresh-map environment step of B environments", "batch": B,
+    print(json.dumps({"metric": "one refill of B spares vs one fresh-map environment step of B environments", "variant": args.variant,
+                      "batch": B,
                       "refill_ms": 1e3 * refill_s, "env_step_kernel_ms": 1e3 * step_s, "ratio": refill_s / step_s}), flush=True)
 
     for every in args.refill_every:
-        env = make_env(B, every)
+        env = make_env(B, every, variant=args.variant)
         gen = torch.Generator(device=env.device)
         gen.manual_seed(1)
         torch.cuda.synchronize()
@@ -115,7 +124,7 @@ def main():
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         loaded, stale = float(env.loaded.sum()), float(env.stale.sum())
-        print(json.dumps({"metric": "map turnover under random actions", "batch": B, "refill_every": every,
+        print(json.dumps({"metric": "map turnover under random actions", "variant": args.variant, "batch": B, "refill_every": every,
                           "run_steps": args.run_steps, "episodes": float(ends), "loaded": loaded, "stale": stale,
                           "stale_share": stale / max(loaded + stale, 1.0),
                           "mean_episode_steps": B * args.run_steps / max(float(ends), 1.0),

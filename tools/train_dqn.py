@@ -3,6 +3,10 @@
 
     python tools/train_dqn.py [--gpus N] [--envs 4096] [--timesteps 4000000] [--gradient-steps 16] [--batch-size 256]
                               [--save DIR] [--resume DIR/checkpoint.pt] [--checkpoint-every STEPS]
+                              [--images] [--fresh-maps] [--per] [--buffer-size N]
+
+`--images` trains dqn.ImageQNetwork on the image environment (rl_env.BatchedImgsEnv); with `--fresh-maps` every episode of it
+starts on a new random map too (map_turnover=True, capacity map_stream.DYNAMIC_CAPACITY, stream seed + rank).
 
 `--save DIR` writes what the reference's run leaves behind (src/test_block_rl.py:73-76,89-96: EvalCallback's best_model and
 model.save's final_model) -- best_model.pt whenever the mean return of a progress window improves, final_model.pt at the end --
@@ -90,6 +94,10 @@ def main():
     ap.add_argument("--fresh-maps", action="store_true",
                     help="a new random map per episode, drawn and planned on the device (generate_map_dynamic; stream seed + rank)")
     ap.add_argument("--seed", type=int, default=0, help="seed of the map stream of --fresh-maps")
+    ap.add_argument("--images", action="store_true",
+                    help="train dqn.ImageQNetwork on the image environment (BatchedImgsEnv); combines with --fresh-maps and --per")
+    ap.add_argument("--buffer-size", type=int, default=None,
+                    help="replay transitions (default 2000000; 200000 with --images, whose transitions hold two uint8 images)")
     args = ap.parse_args()
     if os.environ.get("WORLD_SIZE") is None and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
@@ -102,14 +110,21 @@ def main():
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local))
     rng = np.random.default_rng(100 + rank)
     torch.manual_seed(0)
+    # --images: the image environment; DqnLearner then builds dqn.ImageQNetwork and keeps the images as uint8 in the buffer
     if args.fresh_maps:
-        env = rl_env.BatchedRaysEnv(fresh_start_maps(args.envs, local), device=local, max_episode_steps=400,
-                                    capacity=map_stream.DYNAMIC_CAPACITY)
+        kind = dict(map_turnover=True) if args.images else {}
+        env = (rl_env.BatchedImgsEnv if args.images else rl_env.BatchedRaysEnv)(
+            fresh_start_maps(args.envs, local), device=local, max_episode_steps=400, capacity=map_stream.DYNAMIC_CAPACITY, **kind)
         env.enable_fresh_maps(seed=args.seed + rank)
     else:
-        env = rl_env.BatchedRaysEnv([scene(rng) for _ in range(args.envs)], device=local, max_episode_steps=400)
-    trainer = dqn_train.DqnTrainer(device=f"cuda:{local}", double_q=args.double_q, lr=1e-3)
-    learner = dqn_train.DqnLearner(env, trainer, buffer_size=2_000_000, learning_starts=4 * args.envs,
+        env = (rl_env.BatchedImgsEnv if args.images else rl_env.BatchedRaysEnv)(
+            [scene(rng) for _ in range(args.envs)], device=local, max_episode_steps=400)
+    if args.images and args.graph:
+        sys.exit("train_dqn.py: --graph is not built for --images (the image update runs eagerly)")
+    q_net = dqn_train.ImageQNetwork(env.image_shape) if args.images else None
+    trainer = dqn_train.DqnTrainer(q_net=q_net, device=f"cuda:{local}", double_q=args.double_q, lr=1e-3)
+    buffer_size = args.buffer_size or (200_000 if args.images else 2_000_000)
+    learner = dqn_train.DqnLearner(env, trainer, buffer_size=buffer_size, learning_starts=4 * args.envs,
                                    batch_size=args.batch_size, train_freq=4, gradient_steps=args.gradient_steps,
                                    target_update_interval=200_000, exploration_fraction=0.3, use_graph=args.graph,
                                    track_episodes=False, per=args.per)
@@ -162,7 +177,8 @@ def main():
                           "config": {"workload": "BASELINE.json config 5 (scene 1, medium box, periodic obstacle)",
                                      "envs_per_gpu": args.envs, "timesteps_per_gpu": int(stats["timesteps"]),
                                      "batch_size": args.batch_size, "gradient_steps": args.gradient_steps, "double_q": bool(args.double_q),
-                                     "per": bool(args.per)},
+                                     "per": bool(args.per), "images": bool(args.images), "fresh_maps": bool(args.fresh_maps),
+                                     "buffer_size": buffer_size},
                           "success_rate": stats["success_rate"], "mean_return": stats["mean_return"]}))
     if world > 1:
         dist.destroy_process_group()

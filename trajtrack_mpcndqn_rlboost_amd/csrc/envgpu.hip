@@ -404,6 +404,9 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
                 double* pr = out.pre_reset + (size_t)b * IMG_STATE + IMG_PRE;
                 pr[0] = x; pr[1] = y; pr[2] = th; pr[3] = clock;
                 pr[4] = (out.max_steps > 0 && act && (collided || reached || timeout)) ? 1.0 : 0.0;
+                // the table the row was on at entry (which[b] is flipped further down, after this pass): the record the
+                // image kernel draws the terminal image from
+                if constexpr (FRESH) pr[5] = (double)fr.which[b];
             }
         }
         st[0] = x; st[1] = y; st[2] = th; st[3] = v; st[4] = w; st[5] = clock;

@@ -20,7 +20,8 @@ struct EnvOut {
     // in-kernel auto-reset (max_steps > 0): time-limit flag, and where the observation an episode ENDED in is kept
     uint8_t* truncated; float* term_int; float* term_ext; int max_steps;
     // image variant only (NULL otherwise): per-environment image state (IMG_STATE doubles) that receives, at IMG_PRE..+4,
-    // the pose and clock the step observed BEFORE an in-kernel reset and whether that reset happened
+    // the pose and clock the step observed BEFORE an in-kernel reset and whether that reset happened; the fresh-map step
+    // adds, at IMG_PRE + 5, the record table the row was on when the step began
     double* pre_reset;
 };
 
@@ -31,7 +32,10 @@ struct EnvFresh {
 
 // per-environment image state (mpcgpu_env_img_state_doubles): [0] observations since the last reset, [1..6] obstacle
 // clock of each of the last 6 observations (ring, slot (k - 1) % 6 holds observation k), [7] reserved,
-// [8..11] x, y, theta, clock of the last step before an in-kernel reset, [12] 1 when that reset happened, [13..15] reserved
+// [8..11] x, y, theta, clock of the last step before an in-kernel reset, [12] 1 when that reset happened,
+// [13] fresh-map step only (include/mpcgpu_map.h): 0 / 1, the record table the row was on at the entry of that step -- the
+// record an episode that ended in it ENDED on, while which[b] already names the one the next episode starts on,
+// [14..15] reserved.  [8..13] are hand-over scratch between the two launches of one step, rewritten by every step.
 constexpr int IMG_STATE = 16;
 constexpr int IMG_HIST = 6;
 constexpr int IMG_PRE = 8;

@@ -1,5 +1,5 @@
 // envimg.hip -- image observation of the batched DRL environment (TrajectoryPlannerEnvironmentImgsReward1) for gfx950:
-// the mpcgpu_env_*imgs* entries of include/mpcgpu_env.h.
+// the mpcgpu_env_*imgs* entries of include/mpcgpu_env.h and the fresh-map image step of include/mpcgpu_map.h.
 //
 // A step is two kernels on one stream: env_step_kernel (envgpu.hip) moves the robot and the obstacles and writes the
 // internal observation, reward and flags exactly as for the ray variant; env_img_kernel then draws the two images.
@@ -24,6 +24,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "../../include/mpcgpu_map.h"
 #include "envgpu_internal.hpp"
 
 namespace envimg {
@@ -303,10 +304,22 @@ __device__ void render(const ImgK& k, Shared& sh, EdgePix* epix, const double* r
     __syncthreads();
 }
 
+//
+// FRESH (include/mpcgpu_map.h, mpcgpu_env_step_imgs_fresh_dev): rec_all is the [2][B][rec] table of the fresh-map step and
+// which[b] -- already flipped by env_step_kernel<true> when the row turned over in this step -- names the record the row
+// is on NOW.  The image of the row's current state is drawn from that record; the terminal image of an episode that
+// ended in this step is drawn from the record it ENDED on, whose table index the step left at IMG_PRE + 5.  render()
+// keeps nothing of a record between two calls: it reads the counts from the record it is given and clears the planes, the
+// outline ranges, the row extents and the poses it uses at its start, so the two records of a row may differ in
+// everything.  Stream order is the only synchronisation: this kernel runs behind the step on the caller's stream, and
+// a refill enqueued behind it may overwrite the record a row has just left (its new spare slot) -- by then the terminal
+// image has been drawn.  Everything FRESH adds sits under `if constexpr`.
+template <bool FRESH>
 __global__ __launch_bounds__(THREADS) void env_img_kernel(ImgK k, const double* __restrict__ rec_all,
                                                          const double* __restrict__ state_all, double* img_all,
                                                          const uint8_t* __restrict__ dfield, uint8_t* out_img,
-                                                         uint8_t* term_img, int autoreset, int B) {
+                                                         uint8_t* term_img, int autoreset, int B,
+                                                         const int32_t* __restrict__ which) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ Shared sh;
     const int b = blockIdx.x;
@@ -314,6 +327,7 @@ __global__ __launch_bounds__(THREADS) void env_img_kernel(ImgK k, const double* 
     const int t = threadIdx.x;
     EdgePix* epix = (EdgePix*)dyn;
     const double* rec = rec_all + (size_t)b * k.rec;
+    if constexpr (FRESH) rec = rec_all + ((size_t)(which[b] & 1) * B + b) * k.rec;
     const double* st = state_all + (size_t)b * MPCGPU_ENV_STATE_DOUBLES;
     double* ist = img_all + (size_t)b * IMG_STATE;
     const size_t img_bytes = (size_t)3 * k.H * k.W;
@@ -335,8 +349,15 @@ __global__ __launch_bounds__(THREADS) void env_img_kernel(ImgK k, const double* 
         // up to it; then reset() clears the history (environment.py:161-180)
         if (t == 0) push(ist[IMG_PRE + 3]);
         __syncthreads();
-        if (term_img) render(k, sh, epix, rec, dfield, ist[IMG_PRE], ist[IMG_PRE + 1], ist[IMG_PRE + 2], term_img + b * img_bytes);
+        const double* ended_on = rec;
+        if constexpr (FRESH) ended_on = rec_all + ((size_t)((int)ist[IMG_PRE + 5] & 1) * B + b) * k.rec;
+        if (term_img) render(k, sh, epix, ended_on, dfield, ist[IMG_PRE], ist[IMG_PRE + 1], ist[IMG_PRE + 2], term_img + b * img_bytes);
         if (t == 0) sh.hist[0] = 0.0;
+        // the ring slots past the count are never read; the fresh step clears them all the same, so that the image state
+        // after a turnover is bit for bit the one reset() leaves (step, replace_maps, reset: the form it is tested against)
+        if constexpr (FRESH)
+            if (t == 0)
+                for (int i = 1; i <= IMG_HIST; ++i) sh.hist[i] = 0.0;
     }
     if (t == 0) push(st[5]);
     __syncthreads();
@@ -357,7 +378,8 @@ static int check_img(const mpcgpu_env_img_params* img) {
 
 static int32_t launch(int32_t device, const mpcgpu_env_params* params, const mpcgpu_env_img_params* img, int32_t B,
                       const double* records, double* state, double* img_state, const uint8_t* dfield,
-                      const int32_t* action, envgpu::EnvOut out, uint8_t* obs_image, uint8_t* term_image, void* stream) {
+                      const int32_t* action, envgpu::EnvOut out, uint8_t* obs_image, uint8_t* term_image, void* stream,
+                      const envgpu::EnvFresh* fresh = nullptr) {
     if (check_img(img) != 0) return -1;
     EnvK ek;
     if (!params || !envgpu::layout(*params, ek)) return envgpu::fail("invalid mpcgpu_env_params (P 2..64, M 0..31, K 1..4, E >= 1)");
@@ -366,7 +388,7 @@ static int32_t launch(int32_t device, const mpcgpu_env_params* params, const mpc
         return envgpu::fail("too many outline edges for the image kernel (n_edge_max * 48 bytes + 17 KB must fit 64 KB of LDS)");
     if (B < 0 || !img_state || !dfield || !obs_image) return envgpu::fail("null pointer / negative batch");
     // the step: internal observation, reward, flags; the ray external observation is not written
-    const int rc = envgpu::launch_step(device, params, B, records, state, action, out, false, stream);
+    const int rc = envgpu::launch_step(device, params, B, records, state, action, out, false, stream, fresh);
     if (rc != 0 || B == 0) return rc;
     ImgK k;
     k.rec = ek.rec; k.o_anim = ek.o_anim; k.an = ek.an; k.o_edge = ek.o_edge;
@@ -374,8 +396,14 @@ static int32_t launch(int32_t device, const mpcgpu_env_params* params, const mpc
     k.W = img->width; k.H = img->height;
     k.osx = 2.0 * img->width; k.osy = 2.0 * img->height;
     k.scx = img->scale_x; k.scy = img->scale_y; k.cx = img->center_x; k.cy = img->center_y; k.angle = img->angle;
-    hipLaunchKernelGGL(env_img_kernel, dim3(B), dim3(THREADS), dyn, (hipStream_t)stream, k, records, state, img_state,
-                       dfield, obs_image, term_image, out.pre_reset ? 1 : 0, (int)B);
+    // both launches on the caller's stream, the step first: the image kernel reads the state, the pre-reset block and (fresh)
+    // which[] the step has just written
+    if (fresh)
+        hipLaunchKernelGGL(env_img_kernel<true>, dim3(B), dim3(THREADS), dyn, (hipStream_t)stream, k, records, state, img_state,
+                           dfield, obs_image, term_image, out.pre_reset ? 1 : 0, (int)B, (const int32_t*)fresh->which);
+    else
+        hipLaunchKernelGGL(env_img_kernel<false>, dim3(B), dim3(THREADS), dyn, (hipStream_t)stream, k, records, state, img_state,
+                           dfield, obs_image, term_image, out.pre_reset ? 1 : 0, (int)B, (const int32_t*)nullptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return envgpu::fail("env_img_kernel launch", e);
     return 0;
@@ -413,6 +441,27 @@ int32_t mpcgpu_env_step_imgs_autoreset_dev(int32_t device, const mpcgpu_env_para
                        max_episode_steps, img_state};
     return envimg::launch(device, params, img, B, records, state, img_state, distance_field, action, out, obs_image,
                           terminal_obs_image, stream);
+}
+
+// include/mpcgpu_map.h
+int32_t mpcgpu_env_step_imgs_fresh_dev(int32_t device, const mpcgpu_env_params* params, const mpcgpu_env_img_params* img,
+                                       int32_t B, const double* records2, int32_t* which, int32_t* spare_ready,
+                                       int32_t* loaded, int32_t* stale, double* state, double* img_state,
+                                       const uint8_t* distance_field, const int32_t* action, float* obs_internal,
+                                       uint8_t* obs_image, double* reward, uint8_t* terminated, uint8_t* truncated,
+                                       float* terminal_obs_internal, uint8_t* terminal_obs_image,
+                                       int32_t max_episode_steps, void* stream) {
+    if (!which || !spare_ready || !loaded || !stale) return envgpu::fail("null pointer (which / spare_ready / loaded / stale)");
+    if (!img_state || !distance_field || !obs_image) return envgpu::fail("null pointer (img_state / distance_field / obs_image)");
+    if (max_episode_steps < 0) return envgpu::fail("max_episode_steps must not be negative");
+    if (max_episode_steps > 0 && !action) return envgpu::fail("auto-reset needs actions (max_episode_steps = 0 observes)");
+    if (max_episode_steps > 0 && !truncated) return envgpu::fail("null pointer (truncated)");
+    const bool reset = max_episode_steps > 0;
+    envgpu::EnvOut out{obs_internal, nullptr, reward, terminated, reset ? truncated : nullptr,
+                       reset ? terminal_obs_internal : nullptr, nullptr, max_episode_steps, reset ? img_state : nullptr};
+    const envgpu::EnvFresh fresh{which, spare_ready, loaded, stale};
+    return envimg::launch(device, params, img, B, records2, state, img_state, distance_field, action, out, obs_image,
+                          reset ? terminal_obs_image : nullptr, stream, &fresh);
 }
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 
 The reference draws a new map on every ``reset()`` (``src/pkg_dqn/environment/environment.py:161-169``).  Here every
 environment row owns a current and a spare record, and the fresh-map variant of the auto-reset step
-(``mpcgpu_env_step_fresh_dev``, ``BatchedRaysEnv.enable_spares``) moves a finished row onto its spare inside the launch.
+(``mpcgpu_env_step_fresh_dev``, ``BatchedRaysEnv.enable_spares``) moves a finished row onto its spare inside the launch;
+``mpcgpu_env_step_imgs_fresh_dev`` is the same step for the image environment (``BatchedImgsEnv(map_turnover=True)``).
 
 Maps are drawn from a COUNTER-BASED stream, so that map ``serial`` of stream ``seed`` can be regenerated from these two
 numbers alone, on the host or on the device: :class:`CounterUniform` is a drop-in for the numpy ``Generator`` that
@@ -23,7 +24,7 @@ import numpy as np
 from . import rl_env
 from .solver import MpcGpuError
 
-MAP_EXPORTS = ("mpcgpu_env_step_fresh_dev", "mpcgpu_map_spec_doubles", "mpcgpu_map_draw_dev", "mpcgpu_map_rings_dev",
+MAP_EXPORTS = ("mpcgpu_env_step_fresh_dev", "mpcgpu_env_step_imgs_fresh_dev", "mpcgpu_map_spec_doubles", "mpcgpu_map_draw_dev", "mpcgpu_map_rings_dev",
                "mpcgpu_map_record_dev", "mpcgpu_map_last_error")
 
 # Record-table capacity that holds EVERY generate_map_dynamic draw (derivation: include/mpcgpu_map.h).  Edges: the shrunk hall 4,
@@ -145,10 +146,13 @@ def _bind(lib):
         return lib
     missing = [name for name in MAP_EXPORTS if not hasattr(lib, name)]
     if missing:
-        raise MpcGpuError(f"libmpcgpu.so lacks {missing}: rebuild it (csrc/envgpu.hip, csrc/mapgpu.hip); there is no fallback")
+        raise MpcGpuError(f"libmpcgpu.so lacks {missing}: rebuild it (csrc/envgpu.hip, csrc/envimg.hip, csrc/mapgpu.hip); there is no fallback")
     vp, i32 = C.c_void_p, C.c_int32
     lib.mpcgpu_env_step_fresh_dev.argtypes = [i32, C.POINTER(rl_env._CParams), i32] + [vp] * 14 + [i32, vp]
     lib.mpcgpu_env_step_fresh_dev.restype = i32
+    lib.mpcgpu_env_step_imgs_fresh_dev.argtypes = [i32, C.POINTER(rl_env._CParams), C.POINTER(rl_env._CImgParams), i32] + \
+        [vp] * 16 + [i32, vp]
+    lib.mpcgpu_env_step_imgs_fresh_dev.restype = i32
     lib.mpcgpu_map_spec_doubles.argtypes = []
     lib.mpcgpu_map_spec_doubles.restype = i32
     lib.mpcgpu_map_draw_dev.argtypes = [i32, i32, C.c_uint64] + [vp] * 4

@@ -573,7 +573,13 @@ class BatchedImgsEnv(BatchedRaysEnv):
     ``[B, 3, H, W]``, drawn by a second kernel (``csrc/envimg.hip``): the padded boundary at 255 with the obstacles at 0,
     at the current clock (channel 0) and at the oldest of the last 6 observations since the reset (channel 1), and the
     constant distance field (channel 2).  Every observation pushes that history -- steps, ``observe()``, resets -- and a
-    reset clears it first (environment.py:161-180)."""
+    reset clears it first (environment.py:161-180).
+
+    ``map_turnover=True`` builds the environment for a new map per episode (``include/mpcgpu_map.h``,
+    ``mpcgpu_env_step_imgs_fresh_dev``): :meth:`enable_spares` / :meth:`enable_fresh_maps`, ``load_spares``, ``refill`` and
+    ``current_records`` then work as on :class:`BatchedRaysEnv`.  A row that turns over gets its terminal image from the
+    map its episode ended on and its next observation from the new one.  ``capacity`` sizes the record table for the
+    maps to come; its ``n_edge_max`` must fit the image kernel's edge staging in LDS, which is checked here."""
 
     is_image_env = True
 
@@ -582,8 +588,10 @@ class BatchedImgsEnv(BatchedRaysEnv):
                  cross_track_factor: float = 0.05, reference_speed: float = ROBOT["speed_max"] * 0.8,
                  path_progress_factor: float = 2.0, image_width: int = 54, image_height: int = 54,
                  image_scale_x: float = 1 / 18, image_scale_y: float = 1 / 18, image_down_sample: int = 2,
-                 image_center_x: float = 0.5, image_center_y: float = 0.3, image_angle: float = 0.0):
+                 image_center_x: float = 0.5, image_center_y: float = 0.3, image_angle: float = 0.0,
+                 capacity: Optional[Dict] = None, map_turnover: bool = False):
         lib = _bind(load_library())
+        self.map_turnover = bool(map_turnover)
         self.img_params = image_params(image_width, image_height, image_scale_x, image_scale_y, image_down_sample,
                                        image_center_x, image_center_y, image_angle)
         n_img = lib.mpcgpu_env_img_state_doubles(C.byref(self.img_params))
@@ -592,7 +600,7 @@ class BatchedImgsEnv(BatchedRaysEnv):
         super().__init__(maps, device=device, time_step=time_step, max_episode_steps=max_episode_steps,
                          sample_offset=sample_offset, collision_factor=collision_factor, reach_goal_factor=reach_goal_factor,
                          cross_track_factor=cross_track_factor, reference_speed=reference_speed,
-                         path_progress_factor=path_progress_factor)
+                         path_progress_factor=path_progress_factor, capacity=capacity)
         torch = self._torch
         H, W = int(image_height), int(image_width)
         self.image_shape = (3, H, W)
@@ -601,15 +609,57 @@ class BatchedImgsEnv(BatchedRaysEnv):
         self.term_image = torch.zeros_like(self.obs_image)
         self.distance_field = torch.from_numpy(image_distance_field(W, H, image_scale_x, image_scale_y, image_center_x,
                                                                     image_center_y)).to(self.device).contiguous()
+        if self.map_turnover:
+            # a launch of no rows: the library validates the layout -- n_edge_max against the image kernel's LDS -- and
+            # enqueues nothing
+            rc = lib.mpcgpu_env_step_imgs_dev(self.device_index, C.byref(self.params), C.byref(self.img_params), 0,
+                                              self.records.data_ptr(), self.state.data_ptr(), self.img_state.data_ptr(),
+                                              self.distance_field.data_ptr(), None, self.obs_internal.data_ptr(),
+                                              self.obs_image.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(), None)
+            if rc != 0:
+                raise ValueError(lib.mpcgpu_env_last_error().decode())
+
+    _NO_TURNOVER = ("map turnover on the image environment is chosen at construction: build it with "
+                    "BatchedImgsEnv(..., map_turnover=True) and a capacity= that holds the maps to come")
 
     def enable_spares(self) -> None:
-        raise NotImplementedError("map turnover is built for the ray environment only: the image kernel has no fresh-map variant")
+        """As :meth:`BatchedRaysEnv.enable_spares`, for an environment built with ``map_turnover=True``: from now on every
+        launch is ``mpcgpu_env_step_imgs_fresh_dev`` on the two-record table."""
+        if not self.map_turnover:
+            raise NotImplementedError(self._NO_TURNOVER)
+        super().enable_spares()
 
     def enable_fresh_maps(self, seed: int = 0, refill_every: int = 16) -> None:
-        raise NotImplementedError("map turnover is built for the ray environment only: the image kernel has no fresh-map variant")
+        """As :meth:`BatchedRaysEnv.enable_fresh_maps`, for an environment built with ``map_turnover=True``.  The default
+        ``refill_every`` comes from the same rule, measured on this class: the largest of 1, 4, 8, 16, 32 without a stale
+        reset in 2000 steps of random actions at B = 4096 (``tools/bench_maps.py --variant imgs``,
+        ``profiles/img_fresh_bench.txt``: none up to 16, 0.4 % at 32) -- 16, as for the ray environment."""
+        if not self.map_turnover:
+            raise NotImplementedError(self._NO_TURNOVER)
+        super().enable_fresh_maps(seed=seed, refill_every=refill_every)
+
+    def _fresh_launch(self, actions, max_steps: int) -> None:
+        torch = self._torch
+        aptr = None
+        if actions is not None:
+            actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
+            if actions.shape != (self.B,):
+                raise ValueError(f"actions must have shape ({self.B},)")
+            aptr = actions.data_ptr()
+        rc = self._lib.mpcgpu_env_step_imgs_fresh_dev(
+            self.device_index, C.byref(self.params), C.byref(self.img_params), self.B, self.records2.data_ptr(),
+            self.which.data_ptr(), self.spare_ready.data_ptr(), self.loaded.data_ptr(), self.stale.data_ptr(),
+            self.state.data_ptr(), self.img_state.data_ptr(), self.distance_field.data_ptr(), aptr,
+            self.obs_internal.data_ptr(), self.obs_image.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
+            self.truncated.data_ptr(), self.term_internal.data_ptr(), self.term_image.data_ptr(), int(max_steps),
+            torch.cuda.current_stream(self.device).cuda_stream)
+        if rc != 0:
+            raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
 
     def _launch(self, actions) -> None:
         torch = self._torch
+        if self.records2 is not None:
+            return self._fresh_launch(actions, 0)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         aptr = None
         if actions is not None:
@@ -637,7 +687,7 @@ class BatchedImgsEnv(BatchedRaysEnv):
             mask = torch.ones(self.B, dtype=torch.bool, device=self.device)
         mask = torch.as_tensor(mask, device=self.device).bool()
         fresh = torch.zeros_like(self.state)
-        fresh[:, :5] = self._start
+        fresh[:, :5] = self._start if self.records2 is None else self.records2[self.which.long(), self._rows, 5:10]
         fresh[:, 8:24] = self.state[:, 8:24]
         self.state = torch.where(mask[:, None], fresh, self.state)
         kept = (self.state.clone(), self.img_state.clone(), self.obs_internal.clone(), self.obs_image.clone(),
@@ -654,13 +704,26 @@ class BatchedImgsEnv(BatchedRaysEnv):
         return self._obs()
 
     def state_dict(self) -> Dict:
-        return dict(state=self.state.clone(), img_state=self.img_state.clone(), obs_internal=self.obs_internal.clone(),
-                    obs_image=self.obs_image.clone(), reward=self.reward.clone(), terminated=self.terminated.clone(),
-                    truncated=self.truncated.clone())
+        d = dict(state=self.state.clone(), img_state=self.img_state.clone(), obs_internal=self.obs_internal.clone(),
+                 obs_image=self.obs_image.clone(), reward=self.reward.clone(), terminated=self.terminated.clone(),
+                 truncated=self.truncated.clone())
+        if self.records2 is not None:            # both record tables and the per-row vectors, as BatchedRaysEnv.state_dict
+            d.update({k: getattr(self, k).clone() for k in self._FRESH_KEYS if getattr(self, k, None) is not None})
+            if getattr(self, "refill_every", 0):
+                d["refill_calls"] = self._calls
+        return d
 
     def load_state_dict(self, d: Dict) -> None:
+        if ("records2" in d) != (self.records2 is not None):
+            raise ValueError("state_dict and environment differ in enable_spares()")
         for k in ("state", "img_state", "obs_internal", "obs_image", "reward", "terminated", "truncated"):
             getattr(self, k).copy_(d[k].to(self.device))
+        if self.records2 is not None:
+            for k in self._FRESH_KEYS:
+                if k in d and getattr(self, k, None) is not None:
+                    getattr(self, k).copy_(d[k].to(self.device))
+            if getattr(self, "refill_every", 0):
+                self._calls = int(d.get("refill_calls", 0))
 
     def step(self, actions, auto_reset: bool = False):
         """As :meth:`BatchedRaysEnv.step`; ``obs["external"]`` and ``info["terminal_observation"]["external"]`` are the
@@ -672,6 +735,15 @@ class BatchedImgsEnv(BatchedRaysEnv):
             terminated = self.terminated.bool()
             truncated = (self.state[:, 25] >= self.max_episode_steps) & ~terminated
             return obs, self.reward.clone(), terminated, truncated, {"success": (self.state[:, 7].to(torch.int64) & 4) != 0}
+        if self.records2 is not None:
+            if int(self.max_episode_steps) <= 0:
+                raise MpcGpuError("max_episode_steps must be positive")
+            self._fresh_launch(actions, int(self.max_episode_steps))
+            if getattr(self, "refill_every", 0):     # behind both launches of the step: see include/mpcgpu_map.h
+                self._calls += 1
+                if self._calls % self.refill_every == 0:
+                    self.refill()
+            return self._autoreset_result()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
         if actions.shape != (self.B,):
@@ -684,6 +756,10 @@ class BatchedImgsEnv(BatchedRaysEnv):
             int(self.max_episode_steps), stream)
         if rc != 0:
             raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
+        return self._autoreset_result()
+
+    def _autoreset_result(self):
+        torch = self._torch
         obs = self._obs()
         terminated, truncated = self.terminated.bool(), self.truncated.bool()
         done = terminated | truncated
