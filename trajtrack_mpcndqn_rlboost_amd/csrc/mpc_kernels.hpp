@@ -219,6 +219,24 @@ __host__ __device__ constexpr bool gram_square(int N, int mem) { return MPC_LEAN
 #ifndef MPC_VALUE_ONLY
 #define MPC_VALUE_ONLY 1
 #endif
+// The item phase of eval_point trimmed to its arithmetic for the compiled shape N_hor = 20 (uniform lane split, one problem per
+// wavefront; lean_items() below): the lane roles from 24-bit arithmetic, one lane base per table for the cached dynamic-row trips
+// (the trips are compile-time distances from it: LPS = 3), one definition of the zeros the guarded regions start from, the doubled
+// weights of the gradient read from LDS header slots.  Every floating-point expression, its order and its contraction are as they
+// were: same bits.  0 = the former code, instruction for instruction (`make variants`: libmpcgpu_items0.so, the bitwise yardstick and
+// A/B partner: tests/test_gpu_lean_items.py).  On the MI355X against the parent build (profiles/lean_items_ab.txt): -3.6 % VALU
+// instructions per solve, -1.7 % kernel time on the benchmark leg.
+#ifndef MPC_LEAN_ITEMS
+#define MPC_LEAN_ITEMS 1
+#endif
+// Experiment mask of the four candidates (1 dynamic-row bases, 2 zero materialisations, 4 lane roles, 8 doubled weights).  The count
+// falls with every candidate, the time only with the whole set: no subset that was timed comes within 15 ms of 15 (section 3 of the profile).
+#ifndef MPC_LEAN_ITEMS_SET
+#define MPC_LEAN_ITEMS_SET 15
+#endif
+__host__ __device__ constexpr bool lean_items(int NT, int lanes, bool duo, int what) {
+    return MPC_LEAN_ITEMS != 0 && (MPC_LEAN_ITEMS_SET & what) != 0 && NT == 20 && lanes == 64 && !duo;
+}
 // doubles of the LDS region `gg` (Gram matrices, or the alpha scratch of the two-loop form): see fixed_lds
 __host__ __device__ constexpr int gg_doubles_c(int N, int mem, bool gram) {
     return gram ? yield_even_c(mem * mem + (gram_square(N, mem) ? mem * mem : mem * (mem + 1) / 2)) : yield_even_c(mem);
@@ -927,6 +945,16 @@ constexpr int HD_AKKT = 59;   // LDS header (slots 59..63 are free behind the li
                               // it from scratch in every step (512 B per step and wavefront through an L2 the L-BFGS rings overflow).
 #define KC(i) (cx.hd[KC_BASE + (i)])
 #define HD(i) (cx.hd[(i)])
+// MPC_LEAN_ITEMS, N_hor = 20: the doubled weights of the gradient terms as LDS header slots of their own.  `2.0 * HD(H_ACC) * a` parses
+// as (2 c) a and 2 c is exact: a slot that holds 2 c gives the same bits without forming it in every evaluation.  Slots 26..31 of
+// the LDS header: the workspace record keeps H_ENTRY there, which no kernel reads through the LDS copy.
+enum { H2_ACC = 26, H2_WACC = 27, H2_RV = 28, H2_RW = 29, H2_QVEL = 30, H2_FNPF = 31 /* 2 fleetw npf */ };
+// value of LDS header slot i < KC_BASE of a kernel that runs the lean item phase
+__device__ __forceinline__ double lean_header_slot(const KParams& kp, const double* __restrict__ ws, int i) {
+    const int src = i == H2_ACC ? H_ACC : i == H2_WACC ? H_WACC : i == H2_RV ? H_RV : i == H2_RW ? H_RW : i == H2_QVEL ? H_QVEL : i == H2_FNPF ? H_NPF : i;
+    const double x = ws[src];
+    return i == H2_FNPF ? 2.0 * kp.fleetw * x : i >= H2_ACC ? 2.0 * x : x;
+}
 
 struct EvalOut {
     double psi;             // uniform
@@ -951,7 +979,7 @@ __device__ __forceinline__ void load_problem(const KParams& kp, const double* __
     constexpr bool FIXED = NT != 0 && !P::DUO;
     constexpr FixedLds FL = fixed_lds(NT ? NT : 2, MemOf<NT>::value ? MemOf<NT>::value : 1, false, MINW);  // fields up to `gg` do not depend on where S, Y live
     double* hd = lds + (FIXED ? FL.hd : kp.l_hd);
-    if (lane < KC_BASE) hd[lane] = ws[lane];
+    if (lane < KC_BASE) hd[lane] = lean_items(NT, P::W, P::DUO, 8) ? lean_header_slot(kp, ws, lane) : ws[lane];
     if (lane < 27) hd[KC_BASE + lane] = KTAB[lane];
     cx.hd = hd;
     cx.akkt = hd + HD_AKKT;
@@ -1006,6 +1034,24 @@ struct DynItem {
 // AXIS: every active dynamic row of the batch is an axis-aligned ellipse (angle 0, i.e. cos = 1 and sin = 0 exactly -- what the
 // reference's own prediction feeder produces, src/main.py:77-85): the rotation into the ellipse frame is the identity up to the
 // sign of b.  The general expressions give a = ex and b = -ey EXACTLY in that case (x*1 + y*0), so skipping them changes no bit.
+// the item of the record at e (SC: the centre of (row, step); else the whole record) and, SC, the row constants at s
+template <bool SC, bool AXIS>
+__device__ __forceinline__ DynItem dyn_item_at(const Ctx& cx, const double* e, const double* s, int k, double px, double py) {
+    DynItem d;
+    const double ex = px - e[0], ey = py - e[1];
+    if (SC) {
+        d.wgt = cx.seg[SEGW * k + 8] * s[6];  // q_dyn[k] * alpha, as in dyn_item
+        d.ca = s[0]; d.sa = s[1]; d.ihx = s[2]; d.ihy = s[3]; d.isx = s[4]; d.isy = s[5];
+    } else {
+        d.ca = e[2]; d.sa = e[3]; d.ihx = e[4]; d.ihy = e[5]; d.isx = e[6]; d.isy = e[7]; d.wgt = e[8];
+    }
+    if (AXIS) { d.a = ex; d.b = -ey; }
+    else {
+        d.a = ex * d.ca + ey * d.sa;
+        d.b = ex * d.sa - ey * d.ca;
+    }
+    return d;
+}
 template <bool SC, bool AXIS = false, bool LIN = false>
 __device__ __forceinline__ DynItem dyn_item(const Ctx& cx, int i, int k, int N, double px, double py) {
     DynItem d;
@@ -1082,9 +1128,16 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
     // When 64 is almost a multiple of N (N = 20: 60 lanes) a uniform split is cheaper: the loop strides are constants.
     constexpr int PW = P::W;  // lanes of this problem
     constexpr bool UNIFORM = NT != 0 && (PW % NT) * 5 <= NT;
+    // MPC_LEAN_ITEMS: the candidates of the lean item phase that this instantiation takes (N_hor = 20, uniform split, one problem per wavefront)
+    constexpr bool LI_ROWS = lean_items(NT, PW, P::DUO, 1), LI_ZERO = lean_items(NT, PW, P::DUO, 2), LI_ROLE = lean_items(NT, PW, P::DUO, 4),
+                   LI_HDR = lean_items(NT, PW, P::DUO, 8);
+    if (LI_ROLE) __builtin_assume(lane >= 0 && lane < WAVE);   // the lane index is opaque: 24-bit multiplies, no sign extensions
     const bool c_vl = lane < N;
     const bool c_il = UNIFORM ? lane < (PW / N) * N : true;
-    const int c_ik = lane % N, c_isub = lane / N;
+    // lane / 20 for lane < 64 as (52 lane) >> 10: 52 / 1024 = 1 / 20 + 1 / 1280, and 63 / 1280 < 1 / 20: exact on 0 .. 63
+    auto sub20 = [&]() { return (int)(__umul24((unsigned)lane, 52u) >> 10); };
+    const int c_ik = LI_ROLE ? lane - N * sub20() : lane % N, c_isub = LI_ROLE ? sub20() : lane / N;
+    if (LI_ROLE) __builtin_assume(c_isub >= 0 && c_isub <= (WAVE - 1) / (NT ? NT : 1) && c_ik >= 0 && c_ik < N);   // ... for the table indices made of them
     const int LPS = UNIFORM ? PW / N : (PW - 1 - c_ik) / N + 1;
     constexpr int RV = P::RV, RI = P::RI;
     const int STW = NT ? stash_stride_c(NT, MemOf<NT>::value, MINW) : stash_stride_c(kp.N, kp.mem);   // stash doubles per step
@@ -1178,7 +1231,9 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
 
     // ---- item phase A: stage terms of step ik handled by this lane
     double cost_l = 0.0, S_l = 0.0, gx = 0.0, gy = 0.0, dsx = 0.0, dsy = 0.0;
-    double best = inf, bgx = 0.0, bgy = 0.0;
+    // (MPC_LEAN_ITEMS: the segment minimum starts inside the item lanes' region, its one definition -- no other lane reads it)
+    double best, bgx, bgy;
+    if (!LI_ZERO) { best = inf; bgx = 0.0; bgy = 0.0; }
     double px = 0.0, py = 0.0;
     bool anyh = false;
     // Dynamic rows are visited in TRIPS (trip t: row c_isub + t LPS of every item lane).  Bit t of hmask: some item lane of trip t
@@ -1192,7 +1247,10 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
     // MPC_CACHE_B: d(Ih)/d(position) of this lane's first three rows, zero outside the hard ellipse (see the knob's comment)
     constexpr bool CB = MPC_CACHE_B != 0 && UNIFORM && !P::DUO && NT != 0;
     constexpr bool CB40 = MPC_CACHE_B40 != 0 && NT != 0 && !UNIFORM && !P::DUO && balanced_shape(NT ? NT : 2, MemOf<NT>::value ? MemOf<NT>::value : 1);
-    double cbx0 = 0.0, cby0 = 0.0, cbx1 = 0.0, cby1 = 0.0, cbx2 = 0.0, cby2 = 0.0, cbx3 = 0.0, cby3 = 0.0;
+    // (MPC_LEAN_ITEMS: the pairs of the three cached trips are zeroed once, inside the guard `row < Kd` that phase B repeats before it reads them)
+    constexpr bool LI_TRIPS = LI_ROWS && CB && !LIN;   // the cached trips from one lane base per table (phase A)
+    double cbx0, cby0, cbx1, cby1, cbx2, cby2, cbx3 = 0.0, cby3 = 0.0;
+    if (!(LI_ZERO && CB)) { cbx0 = 0.0; cby0 = 0.0; cbx1 = 0.0; cby1 = 0.0; cbx2 = 0.0; cby2 = 0.0; }
     const int minLPS = UNIFORM ? PW / N : (PW - N) / N + 1;
     // BALANCED WALK (round 4, N_hor = 40).  Steps 0 .. NL2-1 have two item lanes, the NS1 steps behind them ONE: walking the rows
     // step by step, those lanes make Kd trips while the others are done after Kd / 2 -- and the wavefront waits for them.  Here
@@ -1220,6 +1278,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
     if (c_il) {
         const int k = c_ik;
         px = cx.pos[2 * k]; py = cx.pos[2 * k + 1];
+        if (LI_ZERO) { best = inf; bgx = 0.0; bgy = 0.0; }
         // reference-path deviation: min over segments i >= k (mpc_generator.py:207,116-130,28-36).
         // Exact pruning: segments inside a circle that is farther from the robot than sqrt(best) cannot hold the minimum
         // (nor tie with it), so their distances are not evaluated; the value and the arg-min are unchanged.
@@ -1439,14 +1498,74 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
             }
             return Ih > 0.0;
         };
-        if (CB) {
+        // MPC_LEAN_ITEMS: the body of dyn_a1, expression for expression, on an item d that the caller read at a compile-time distance
+        // from the lane's base (Hrow = cx.H + row)
+        auto dyn_a1_of = [&](const DynItem& d, double* Hrow, double& tx, double& ty) -> bool {
+            const double a2 = d.a * d.a, b2 = d.b * d.b;
+            const double Ih = 1.0 - a2 * d.ihx - b2 * d.ihy;
+            if (Ih > 0.0) {
+                lds_add(Hrow, Ih);
+                if (CB && want_grad) {
+                    if (AXIS) {
+                        tx = -2.0 * d.a * d.ihx;
+                        ty = 2.0 * d.b * d.ihy;
+                    } else {
+                        tx = -2.0 * d.a * d.ca * d.ihx - 2.0 * d.b * d.sa * d.ihy;
+                        ty = -2.0 * d.a * d.sa * d.ihx + 2.0 * d.b * d.ca * d.ihy;
+                    }
+                }
+            }
+            const double Is = 1.0 - a2 * d.isx - b2 * d.isy;
+            if (Is > 0.0) {
+                cost_l += d.wgt * Is * Is;
+                const double wI = 2.0 * d.wgt * Is;
+                if (VO) {
+                } else if (AXIS) {
+                    gx += wI * (-2.0 * d.a * d.isx);
+                    gy += wI * (2.0 * d.b * d.isy);
+                } else {
+                    gx += wI * (-2.0 * d.a * d.ca * d.isx - 2.0 * d.b * d.sa * d.isy);
+                    gy += wI * (-2.0 * d.a * d.sa * d.isx + 2.0 * d.b * d.ca * d.isy);
+                }
+            }
+            return Ih > 0.0;
+        };
+        if (LI_TRIPS) {
+            // The cached trips from ONE lane base per table: LPS is the constant 3 here, so the rows of trips 1 and 2 sit at compile-time
+            // distances from trip 0's record and go into the offset field of the LDS instructions.  (sub N + k is the lane index.)
+            constexpr int RECW = SC ? DYNP : DYNW, LP = PW / (NT ? NT : 1);
+            const double* e0 = cx.dyn + lane * RECW;
+            const double* s0 = cx.dync + c_isub * DYNC;
+            double* H0 = cx.H + c_isub;
+            auto trip = [&](int t, double& tx, double& ty) {
+                if (c_isub + t * LP < cx.Kd) {
+                    if (LI_ZERO) { tx = 0.0; ty = 0.0; }
+                    anyh |= dyn_a1_of(dyn_item_at<SC, AXIS>(cx, e0 + t * LP * N * RECW, s0 + t * LP * DYNC, k, px, py), H0 + t * LP, tx, ty);
+                }
+            };
+            trip(0, cbx0, cby0);
+            trip(1, cbx1, cby1);
+            trip(2, cbx2, cby2);
+            double ux, uy;      // rows beyond the cached trips: phase B re-derives them
+            MPC_ITEM_LOOP
+            for (int i = c_isub + 3 * LP; i < cx.Kd; i += LPS) anyh |= dyn_a1(i, ux, uy);
+        } else if (CB) {
             int i = c_isub;
+            if (LI_ZERO) {
+                if (i < cx.Kd) { cbx0 = 0.0; cby0 = 0.0; anyh |= dyn_a1(i, cbx0, cby0); }
+                i += LPS;
+                if (i < cx.Kd) { cbx1 = 0.0; cby1 = 0.0; anyh |= dyn_a1(i, cbx1, cby1); }
+                i += LPS;
+                if (i < cx.Kd) { cbx2 = 0.0; cby2 = 0.0; anyh |= dyn_a1(i, cbx2, cby2); }
+                i += LPS;
+            } else {
             if (i < cx.Kd) anyh |= dyn_a1(i, cbx0, cby0);
             i += LPS;
             if (i < cx.Kd) anyh |= dyn_a1(i, cbx1, cby1);
             i += LPS;
             if (i < cx.Kd) anyh |= dyn_a1(i, cbx2, cby2);
             i += LPS;
+            }
             double ux, uy;      // rows beyond the cached trips: phase B re-derives them
             MPC_ITEM_LOOP
             for (; i < cx.Kd; i += LPS) anyh |= dyn_a1(i, ux, uy);
@@ -1566,12 +1685,21 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
             } else if (any_h && CB) {
                 // the cached trips: W_i times the factor phase A left (zero where the position is outside the ellipse: gx + W_i * 0 = gx)
                 int i = c_isub;
+                if (LI_ROWS) {   // the row weights of the three trips from one lane base
+                    constexpr int LP = PW / (NT ? NT : 1);
+                    const double* W0 = cx.W + c_isub;
+                    if (c_isub < cx.Kd) { const double wi = W0[0]; gx += wi * cbx0; gy += wi * cby0; }
+                    if (c_isub + LP < cx.Kd) { const double wi = W0[LP]; gx += wi * cbx1; gy += wi * cby1; }
+                    if (c_isub + 2 * LP < cx.Kd) { const double wi = W0[2 * LP]; gx += wi * cbx2; gy += wi * cby2; }
+                    i += 3 * LP;
+                } else {
                 if (i < cx.Kd) { const double wi = cx.W[i]; gx += wi * cbx0; gy += wi * cby0; }
                 i += LPS;
                 if (i < cx.Kd) { const double wi = cx.W[i]; gx += wi * cbx1; gy += wi * cby1; }
                 i += LPS;
                 if (i < cx.Kd) { const double wi = cx.W[i]; gx += wi * cbx2; gy += wi * cby2; }
                 i += LPS;
+                }
                 MPC_ITEM_LOOP
                 for (; i < cx.Kd; i += LPS) {
                     const DynItem d = dyn_item<SC, AXIS, LIN>(cx, i, k, N, px, py);
@@ -1672,8 +1800,8 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
         Gx += HD(H_QRPD) * wbx; Gy += HD(H_QRPD) * wby;
         vcost = HD(H_QRPD) * bb;
         if (cx.pad_f && kp.W2 - r2o > 0.0) {
-            Gx -= 2.0 * fleetw * HD(H_NPF) * X;
-            Gy -= 2.0 * fleetw * HD(H_NPF) * Y;
+            Gx -= (LI_HDR ? HD(H2_FNPF) : 2.0 * fleetw * HD(H_NPF)) * X;
+            Gy -= (LI_HDR ? HD(H2_FNPF) : 2.0 * fleetw * HD(H_NPF)) * Y;
         }
     }
 
@@ -1724,11 +1852,11 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
 
     PROF_MARK(8);  // vector terms + psi
     if (want_grad) {
-        const double da = c_vl ? (2.0 * HD(H_ACC) * a + c * ea) * kp.inv_ts : 0.0;
-        const double db = c_vl ? (2.0 * HD(H_WACC) * bacc + c * eb) * kp.inv_ts : 0.0;
+        const double da = c_vl ? ((LI_HDR ? HD(H2_ACC) : 2.0 * HD(H_ACC)) * a + c * ea) * kp.inv_ts : 0.0;
+        const double db = c_vl ? ((LI_HDR ? HD(H2_WACC) : 2.0 * HD(H_WACC)) * bacc + c * eb) * kp.inv_ts : 0.0;
         const double da_n = shift_down1(da), db_n = shift_down1(db);
-        double gv = 2.0 * HD(H_QVEL) * (v - cx.vref) + 2.0 * HD(H_RV) * v + da - da_n;
-        double gw = 2.0 * HD(H_RW) * w + db - db_n;
+        double gv = (LI_HDR ? HD(H2_QVEL) : 2.0 * HD(H_QVEL)) * (v - cx.vref) + (LI_HDR ? HD(H2_RV) : 2.0 * HD(H_RV)) * v + da - da_n;
+        double gw = (LI_HDR ? HD(H2_RW) : 2.0 * HD(H_RW)) * w + db - db_n;
         // adjoint of the rollout: suffix sums instead of a serial backward sweep
         // (kept in registers they are finite beyond the horizon, where v = 0 and the adjoint sums Ax, Ay are 0: same bits)
         double Cx = kCx, Sy = kSy, dCw = kdCw, dSw = kdSw;

@@ -150,7 +150,7 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
     {
         cx.lane = lane; cx.vl = lane < N; cx.il = true; cx.ik = lane % N; cx.isub = lane / N;
         double* hd = lds + kp.l_hd;
-        if (threadIdx.x < KC_BASE) hd[threadIdx.x] = ws[threadIdx.x];
+        if (threadIdx.x < KC_BASE) hd[threadIdx.x] = lean_items(NT, WAVE, false, 8) ? lean_header_slot(kp, ws, (int)threadIdx.x) : ws[threadIdx.x];
         if (threadIdx.x >= WAVE && threadIdx.x < WAVE + 27) hd[KC_BASE + threadIdx.x - WAVE] = KTAB[threadIdx.x - WAVE];
         cx.hd = hd;
         cx.akkt = lds + kp.l_xch + wid * TEAM_XCH + 2;   // this wavefront's own slot of the exchange area ([0], [1]: verdict banks, [7]: clock)
