@@ -105,7 +105,7 @@ def main():
     print(json.dumps(line), flush=True)
 
     acts = torch.randint(0, 9, (B,), device=env.device, dtype=torch.int32)
-    step_s = time_launches(lambda: env._fresh_launch(acts, env.max_episode_steps), args.steps, args.warmup)
+    step_s = time_launches(lambda: env._launch(acts, env.max_episode_steps), args.steps, args.warmup)
     print(json.dumps({"metric": "one refill of B spares vs one fresh-map environment step of B environments", "variant": args.variant,
                       "batch": B,
                       "refill_ms": 1e3 * refill_s, "env_step_kernel_ms": 1e3 * step_s, "ratio": refill_s / step_s}), flush=True)

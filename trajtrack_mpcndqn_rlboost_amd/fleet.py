@@ -12,9 +12,15 @@ from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from .solver import CTracker, MpcGpuError
+from .solver import CTracker, bind_exports
 
-FLEET_EXPORTS = ("mpcgpu_fleet_share_dev", "mpcgpu_tracker_step_rows_dev")
+_VP, _I32 = C.c_void_p, C.c_int32
+# export -> (restype, argtypes); include/mpcgpu_fleet.h
+_FLEET_TABLE = {
+    "mpcgpu_fleet_share_dev": (_I32, [_VP, _I32, _I32] + [_VP] * 6 + [_VP]),
+    "mpcgpu_tracker_step_rows_dev": (_I32, [_VP, C.POINTER(CTracker), _VP, _I32, _I32, _VP] + [_VP] * 8 + [_VP]),
+}
+FLEET_EXPORTS = tuple(_FLEET_TABLE)
 
 
 class GroupTable(NamedTuple):
@@ -75,15 +81,4 @@ def check_rows(rows, B: int) -> np.ndarray:
 
 
 def _bind(lib):
-    if getattr(lib, "_fleet_bound", False):
-        return lib
-    missing = [name for name in FLEET_EXPORTS if not hasattr(lib, name)]
-    if missing:
-        raise MpcGpuError(f"libmpcgpu.so lacks {missing}: rebuild it (csrc/trackgpu.hip, csrc/mpcgpu.hip); there is no fallback")
-    vp, i32 = C.c_void_p, C.c_int32
-    lib.mpcgpu_fleet_share_dev.argtypes = [vp, i32, i32] + [vp] * 6 + [vp]
-    lib.mpcgpu_fleet_share_dev.restype = i32
-    lib.mpcgpu_tracker_step_rows_dev.argtypes = [vp, C.POINTER(CTracker), vp, i32, i32, vp] + [vp] * 8 + [vp]
-    lib.mpcgpu_tracker_step_rows_dev.restype = i32
-    lib._fleet_bound = True
-    return lib
+    return bind_exports(lib, "fleet", _FLEET_TABLE, "csrc/trackgpu.hip, csrc/mpcgpu.hip")

@@ -22,10 +22,20 @@ from typing import Dict, Sequence
 import numpy as np
 
 from . import rl_env
-from .solver import MpcGpuError
+from .solver import MpcGpuError, bind_exports
 
-MAP_EXPORTS = ("mpcgpu_env_step_fresh_dev", "mpcgpu_env_step_imgs_fresh_dev", "mpcgpu_map_spec_doubles", "mpcgpu_map_draw_dev", "mpcgpu_map_rings_dev",
-               "mpcgpu_map_record_dev", "mpcgpu_map_last_error")
+_VP, _I32, _PP = C.c_void_p, C.c_int32, C.POINTER(rl_env._CParams)
+# export -> (restype, argtypes); include/mpcgpu_map.h
+_MAP_TABLE = {
+    "mpcgpu_env_step_fresh_dev": (_I32, [_I32, _PP, _I32] + [_VP] * 14 + [_I32, _VP]),
+    "mpcgpu_env_step_imgs_fresh_dev": (_I32, [_I32, _PP, C.POINTER(rl_env._CImgParams), _I32] + [_VP] * 16 + [_I32, _VP]),
+    "mpcgpu_map_spec_doubles": (_I32, []),
+    "mpcgpu_map_draw_dev": (_I32, [_I32, _I32, C.c_uint64] + [_VP] * 4),
+    "mpcgpu_map_rings_dev": (_I32, [_I32, _I32] + [_VP] * 5),
+    "mpcgpu_map_record_dev": (_I32, [_I32, _PP, _I32] + [_VP] * 9),
+    "mpcgpu_map_last_error": (C.c_char_p, []),
+}
+MAP_EXPORTS = tuple(_MAP_TABLE)
 
 # Record-table capacity that holds EVERY generate_map_dynamic draw (derivation: include/mpcgpu_map.h).  Edges: the shrunk hall 4,
 # three boxes of 4 corners x 5 points, seven convex 12-corner ellipses of at most 16 + 24 points: 4 + 60 + 280.  A path bends at
@@ -142,29 +152,7 @@ def unpack_specs(table: np.ndarray):
 
 
 def _bind(lib):
-    if getattr(lib, "_map_bound", False):
-        return lib
-    missing = [name for name in MAP_EXPORTS if not hasattr(lib, name)]
-    if missing:
-        raise MpcGpuError(f"libmpcgpu.so lacks {missing}: rebuild it (csrc/envgpu.hip, csrc/envimg.hip, csrc/mapgpu.hip); there is no fallback")
-    vp, i32 = C.c_void_p, C.c_int32
-    lib.mpcgpu_env_step_fresh_dev.argtypes = [i32, C.POINTER(rl_env._CParams), i32] + [vp] * 14 + [i32, vp]
-    lib.mpcgpu_env_step_fresh_dev.restype = i32
-    lib.mpcgpu_env_step_imgs_fresh_dev.argtypes = [i32, C.POINTER(rl_env._CParams), C.POINTER(rl_env._CImgParams), i32] + \
-        [vp] * 16 + [i32, vp]
-    lib.mpcgpu_env_step_imgs_fresh_dev.restype = i32
-    lib.mpcgpu_map_spec_doubles.argtypes = []
-    lib.mpcgpu_map_spec_doubles.restype = i32
-    lib.mpcgpu_map_draw_dev.argtypes = [i32, i32, C.c_uint64] + [vp] * 4
-    lib.mpcgpu_map_draw_dev.restype = i32
-    lib.mpcgpu_map_rings_dev.argtypes = [i32, i32] + [vp] * 5
-    lib.mpcgpu_map_rings_dev.restype = i32
-    lib.mpcgpu_map_record_dev.argtypes = [i32, C.POINTER(rl_env._CParams), i32] + [vp] * 9
-    lib.mpcgpu_map_record_dev.restype = i32
-    lib.mpcgpu_map_last_error.argtypes = []
-    lib.mpcgpu_map_last_error.restype = C.c_char_p
-    lib._map_bound = True
-    return lib
+    return bind_exports(lib, "map", _MAP_TABLE, "csrc/envgpu.hip, csrc/envimg.hip, csrc/mapgpu.hip")
 
 
 def draw_specs_dev(spec_table, spare_ready, attempt, seed: int, device: int = 0):

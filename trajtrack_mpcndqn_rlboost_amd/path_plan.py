@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import rl_geometry as rg
-from .solver import MpcGpuError, load_library
+from .solver import MpcGpuError, bind_exports, load_library
 
 MAX_VERTICES = 256
 MAX_RINGS = 32
@@ -25,24 +25,18 @@ class _CPlanParams(C.Structure):
     _fields_ = [("n_vert_max", C.c_int32), ("n_ring_max", C.c_int32), ("n_node_max", C.c_int32), ("reserved", C.c_int32)]
 
 
-PLAN_EXPORTS = ("mpcgpu_plan_record_doubles", "mpcgpu_plan_paths_dev", "mpcgpu_plan_last_error")
+_VP, _I32, _PP = C.c_void_p, C.c_int32, C.POINTER(_CPlanParams)
+# export -> (restype, argtypes); include/mpcgpu_plan.h
+_PLAN_TABLE = {
+    "mpcgpu_plan_record_doubles": (_I32, [_PP]),
+    "mpcgpu_plan_paths_dev": (_I32, [_I32, _PP, _I32] + [_VP] * 7),
+    "mpcgpu_plan_last_error": (C.c_char_p, []),
+}
+PLAN_EXPORTS = tuple(_PLAN_TABLE)
 
 
 def _bind(lib):
-    if getattr(lib, "_plan_bound", False):
-        return lib
-    missing = [name for name in PLAN_EXPORTS if not hasattr(lib, name)]
-    if missing:
-        raise MpcGpuError(f"libmpcgpu.so lacks {missing}: rebuild it (csrc/plangpu.hip); there is no fallback")
-    vp, pp, i32 = C.c_void_p, C.POINTER(_CPlanParams), C.c_int32
-    lib.mpcgpu_plan_record_doubles.argtypes = [pp]
-    lib.mpcgpu_plan_record_doubles.restype = i32
-    lib.mpcgpu_plan_paths_dev.argtypes = [i32, pp, i32] + [vp] * 7
-    lib.mpcgpu_plan_paths_dev.restype = i32
-    lib.mpcgpu_plan_last_error.argtypes = []
-    lib.mpcgpu_plan_last_error.restype = C.c_char_p
-    lib._plan_bound = True
-    return lib
+    return bind_exports(lib, "plan", _PLAN_TABLE, "csrc/plangpu.hip")
 
 
 def oriented_rings(boundary, obstacles: Sequence) -> List[np.ndarray]:

@@ -11,7 +11,7 @@ from typing import Tuple
 
 import torch
 
-from .solver import MpcGpuError, load_library
+from .solver import MpcGpuError, bind_exports, load_library
 
 MAX_ROWS = 4096
 
@@ -21,29 +21,22 @@ class _CPerParams(C.Structure):
                 ("epsilon", C.c_double), ("initial_priority", C.c_double)]
 
 
-PER_EXPORTS = ("mpcgpu_per_state_doubles", "mpcgpu_per_reset_dev", "mpcgpu_per_add_dev", "mpcgpu_per_update_dev",
-               "mpcgpu_per_sample_dev", "mpcgpu_per_stats_dev", "mpcgpu_per_last_error")
+_VP, _I32, _I64, _PP = C.c_void_p, C.c_int32, C.c_int64, C.POINTER(_CPerParams)
+# export -> (restype, argtypes); include/mpcgpu_per.h
+_PER_TABLE = {
+    "mpcgpu_per_state_doubles": (_I32, []),
+    "mpcgpu_per_reset_dev": (_I32, [_I32, _PP, _VP, _VP, _VP]),
+    "mpcgpu_per_add_dev": (_I32, [_I32, _PP, _VP, _VP, _I64, _I64, _I64, _VP]),
+    "mpcgpu_per_update_dev": (_I32, [_I32, _PP, _VP, _VP, _VP, _I32, _VP]),
+    "mpcgpu_per_sample_dev": (_I32, [_I32, _PP, _VP, _VP, _I32, _I64, _VP, _VP, _VP, _VP]),
+    "mpcgpu_per_stats_dev": (_I32, [_I32, _PP, _VP, _VP, _VP, _VP]),
+    "mpcgpu_per_last_error": (C.c_char_p, []),
+}
+PER_EXPORTS = tuple(_PER_TABLE)
 
 
 def _bind(lib):
-    if getattr(lib, "_per_bound", False):
-        return lib
-    missing = [name for name in PER_EXPORTS if not hasattr(lib, name)]
-    if missing:
-        raise MpcGpuError(f"libmpcgpu.so lacks {missing}: rebuild it (csrc/pergpu.hip); there is no fallback")
-    vp, pp, i32, i64 = C.c_void_p, C.POINTER(_CPerParams), C.c_int32, C.c_int64
-    lib.mpcgpu_per_state_doubles.argtypes = []
-    lib.mpcgpu_per_reset_dev.argtypes = [i32, pp, vp, vp, vp]
-    lib.mpcgpu_per_add_dev.argtypes = [i32, pp, vp, vp, i64, i64, i64, vp]
-    lib.mpcgpu_per_update_dev.argtypes = [i32, pp, vp, vp, vp, i32, vp]
-    lib.mpcgpu_per_sample_dev.argtypes = [i32, pp, vp, vp, i32, i64, vp, vp, vp, vp]
-    lib.mpcgpu_per_stats_dev.argtypes = [i32, pp, vp, vp, vp, vp]
-    for name in PER_EXPORTS[:-1]:
-        getattr(lib, name).restype = i32
-    lib.mpcgpu_per_last_error.argtypes = []
-    lib.mpcgpu_per_last_error.restype = C.c_char_p
-    lib._per_bound = True
-    return lib
+    return bind_exports(lib, "per", _PER_TABLE, "csrc/pergpu.hip")
 
 
 class SumTree:

@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import rl_geometry as rg
-from .solver import MpcGpuError, load_library
+from .solver import MpcGpuError, bind_exports, load_library
 
 STATE_DOUBLES = 32
 N_INTERNAL = 14
@@ -129,31 +129,22 @@ class _CImgParams(C.Structure):
                 ("angle", C.c_double)]
 
 
-ENV_EXPORTS = ("mpcgpu_env_record_doubles", "mpcgpu_env_step_dev", "mpcgpu_env_step_autoreset_dev", "mpcgpu_env_last_error",
-               "mpcgpu_env_img_state_doubles", "mpcgpu_env_step_imgs_dev", "mpcgpu_env_step_imgs_autoreset_dev")
+_VP, _I32, _PP, _IP = C.c_void_p, C.c_int32, C.POINTER(_CParams), C.POINTER(_CImgParams)
+# export -> (restype, argtypes); include/mpcgpu_env.h
+_ENV_TABLE = {
+    "mpcgpu_env_record_doubles": (_I32, [_PP]),
+    "mpcgpu_env_step_dev": (_I32, [_I32, _PP, _I32] + [_VP] * 8),
+    "mpcgpu_env_step_autoreset_dev": (_I32, [_I32, _PP, _I32] + [_VP] * 10 + [_I32, _VP]),
+    "mpcgpu_env_last_error": (C.c_char_p, []),
+    "mpcgpu_env_img_state_doubles": (_I32, [_IP]),
+    "mpcgpu_env_step_imgs_dev": (_I32, [_I32, _PP, _IP, _I32] + [_VP] * 10),
+    "mpcgpu_env_step_imgs_autoreset_dev": (_I32, [_I32, _PP, _IP, _I32] + [_VP] * 12 + [_I32, _VP]),
+}
+ENV_EXPORTS = tuple(_ENV_TABLE)
 
 
 def _bind(lib):
-    if getattr(lib, "_env_bound", False):
-        return lib
-    vp = C.c_void_p
-    lib.mpcgpu_env_record_doubles.argtypes = [C.POINTER(_CParams)]
-    lib.mpcgpu_env_record_doubles.restype = C.c_int32
-    lib.mpcgpu_env_step_dev.argtypes = [C.c_int32, C.POINTER(_CParams), C.c_int32] + [vp] * 8
-    lib.mpcgpu_env_step_dev.restype = C.c_int32
-    lib.mpcgpu_env_step_autoreset_dev.argtypes = [C.c_int32, C.POINTER(_CParams), C.c_int32] + [vp] * 10 + [C.c_int32, vp]
-    lib.mpcgpu_env_step_autoreset_dev.restype = C.c_int32
-    ip = C.POINTER(_CImgParams)
-    lib.mpcgpu_env_img_state_doubles.argtypes = [ip]
-    lib.mpcgpu_env_img_state_doubles.restype = C.c_int32
-    lib.mpcgpu_env_step_imgs_dev.argtypes = [C.c_int32, C.POINTER(_CParams), ip, C.c_int32] + [vp] * 10
-    lib.mpcgpu_env_step_imgs_dev.restype = C.c_int32
-    lib.mpcgpu_env_step_imgs_autoreset_dev.argtypes = [C.c_int32, C.POINTER(_CParams), ip, C.c_int32] + [vp] * 12 + [C.c_int32, vp]
-    lib.mpcgpu_env_step_imgs_autoreset_dev.restype = C.c_int32
-    lib.mpcgpu_env_last_error.argtypes = []
-    lib.mpcgpu_env_last_error.restype = C.c_char_p
-    lib._env_bound = True
-    return lib
+    return bind_exports(lib, "env", _ENV_TABLE, "csrc/envgpu.hip, csrc/envimg.hip")
 
 
 def path_lengths(path: np.ndarray):
@@ -218,6 +209,11 @@ def pack_records(maps: Sequence[Dict], n_kf_max: int = 2, limits: Optional[Dict]
         blk[:len(edges)] = np.asarray(edges)
         r[o_edge:o_edge + 5 * E] = blk.reshape(-1)
     return rec, dict(n_path_max=P, n_obst_max=M, n_kf_max=K, n_edge_max=E)
+
+
+def _over(mask, like):
+    """A row mask [B] shaped to broadcast over ``like`` [B, ...]."""
+    return mask.reshape((-1,) + (1,) * (like.dim() - 1))
 
 
 class BatchedRaysEnv:
@@ -348,23 +344,6 @@ class BatchedRaysEnv:
             return self.records.clone()
         return self.records2[self.which.long(), self._rows]
 
-    def _fresh_launch(self, actions, max_steps: int) -> None:
-        torch = self._torch
-        aptr = None
-        if actions is not None:
-            actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
-            if actions.shape != (self.B,):
-                raise ValueError(f"actions must have shape ({self.B},)")
-            aptr = actions.data_ptr()
-        rc = self._lib.mpcgpu_env_step_fresh_dev(
-            self.device_index, C.byref(self.params), self.B, self.records2.data_ptr(), self.which.data_ptr(),
-            self.spare_ready.data_ptr(), self.loaded.data_ptr(), self.stale.data_ptr(), self.state.data_ptr(), aptr,
-            self.obs_internal.data_ptr(), self.obs_external.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
-            self.truncated.data_ptr(), self.term_internal.data_ptr(), self.term_external.data_ptr(), int(max_steps),
-            torch.cuda.current_stream(self.device).cuda_stream)
-        if rc != 0:
-            raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
-
     def replace_maps(self, rows, maps: Sequence[Dict]) -> None:
         """Give environments ``rows`` the new ``maps`` (:func:`make_map`, e.g. with a path of ``path_plan``): their rows
         of the device record table are re-packed in place, no other row is touched.  Raises ``ValueError``, before
@@ -377,8 +356,7 @@ class BatchedRaysEnv:
             raise ValueError(f"replace_maps needs one map per row, rows distinct and in [0, {self.B})")
         if not rows:
             return
-        limits = {k: getattr(self.params, k) for k in ("n_path_max", "n_obst_max", "n_kf_max", "n_edge_max")}
-        rec, _ = pack_records(maps, limits=limits)
+        rec, _ = pack_records(maps, limits=self._limits())
         assert rec.shape[1] == self.records.shape[1]
         idx = torch.as_tensor(rows, dtype=torch.int64, device=self.device)
         start = np.stack([np.asarray(m["start"], dtype=np.float64) for m in maps])
@@ -388,60 +366,82 @@ class BatchedRaysEnv:
         self.records[idx] = torch.from_numpy(rec).to(self.device)
         self._start[idx] = torch.from_numpy(start).to(self.device)
 
+    # ---- what the image variant describes differently ---------------------------------------------------------------
+    _EXTERNAL = ("obs_external", "term_external")    # attributes: the external observation and its terminal copy
+    _ROW_STATE = ("state",)                          # per-row state tensors, saved in state_dict under these names ...
+    _RESET_CLEARS = ()                               # ... and those of them a reset zeroes for the rows it resets
+    _ENTRIES = ("mpcgpu_env_step_dev", "mpcgpu_env_step_autoreset_dev", "mpcgpu_env_step_fresh_dev")
+
+    def _args(self, table: tuple, aptr, max_steps) -> tuple:
+        """The arguments of a C entry but the stream: ``table`` are the pointers of the record table (and of the spare
+        vectors with it), ``max_steps`` is None for the plain entry, which ends after ``terminated``."""
+        tail = () if max_steps is None else (self.truncated.data_ptr(), self.term_internal.data_ptr(),
+                                             self.term_external.data_ptr(), max_steps)
+        return (self.device_index, C.byref(self.params), self.B, *table, self.state.data_ptr(), aptr,
+                self.obs_internal.data_ptr(), self.obs_external.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
+                *tail)
+
     # ---- kernel launch ---------------------------------------------------------------------------------------------
-    def _launch(self, actions) -> None:
+    def _launch(self, actions, max_steps: int = 0) -> None:
+        """Enqueue one step on the current stream: the fresh-table entry once :meth:`enable_spares` ran, otherwise the
+        auto-reset entry when ``max_steps > 0``, otherwise the plain one.  ``actions=None`` observes (no auto-reset
+        then)."""
         torch = self._torch
-        if self.records2 is not None:
-            return self._fresh_launch(actions, 0)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         aptr = None
         if actions is not None:
-            actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
+            actions = torch.as_tensor(actions, dtype=torch.int32, device=self.device).contiguous()
             if actions.shape != (self.B,):
                 raise ValueError(f"actions must have shape ({self.B},)")
             aptr = actions.data_ptr()
-        rc = self._lib.mpcgpu_env_step_dev(self.device_index, C.byref(self.params), self.B, self.records.data_ptr(),
-                                           self.state.data_ptr(), aptr, self.obs_internal.data_ptr(),
-                                           self.obs_external.data_ptr(), self.reward.data_ptr(),
-                                           self.terminated.data_ptr(), stream)
+        plain, autoreset, fresh = self._ENTRIES
+        if self.records2 is not None:
+            entry, table = fresh, (self.records2.data_ptr(), self.which.data_ptr(), self.spare_ready.data_ptr(),
+                                   self.loaded.data_ptr(), self.stale.data_ptr())
+        else:
+            entry, table = (autoreset if max_steps > 0 else plain), (self.records.data_ptr(),)
+        rc = getattr(self._lib, entry)(*self._args(table, aptr, None if entry == plain else int(max_steps)),
+                                       torch.cuda.current_stream(self.device).cuda_stream)
         if rc != 0:
             raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
 
     def _obs(self) -> Dict[str, "object"]:
-        return {"internal": self.obs_internal.clone(), "external": self.obs_external.clone()}
+        return {"internal": self.obs_internal.clone(), "external": getattr(self, self._EXTERNAL[0]).clone()}
 
     # ---- gym-style API ---------------------------------------------------------------------------------------------
     def reset(self, mask=None):
-        """Reset all (or the masked) environments to their map's start state (environment.py:166-186).  The
-        observation memory is NOT cleared: the reference's component keeps ``old_obs`` across episodes."""
+        """Reset all (or the masked) environments to their map's start state (environment.py:166-186); the image
+        variant clears their image history first (environment.py:161-180).  The observation memory is NOT cleared: the
+        reference's component keeps ``old_obs`` across episodes."""
         torch = self._torch
         if mask is None:
             mask = torch.ones(self.B, dtype=torch.bool, device=self.device)
         mask = torch.as_tensor(mask, device=self.device).bool()
-        keep = self.state[:, 8:24].clone()
         fresh = torch.zeros_like(self.state)
         fresh[:, :5] = self._start if self.records2 is None else self.records2[self.which.long(), self._rows, 5:10]
-        fresh[:, 8:24] = keep
-        self.state = torch.where(mask[:, None], fresh, self.state)
+        fresh[:, 8:24] = self.state[:, 8:24]
+        self.state = torch.where(_over(mask, fresh), fresh, self.state)
         # update_status(reset=True) + get_observation for the reset rows only: the launch observes every environment, so the
         # rows that are NOT reset get their state, observation (including its one-step memory half), reward and
         # termination flag restored afterwards -- a partial reset must leave them bit-identical
-        others = self.state.clone()
-        kept = (self._obs(), self.reward.clone(), self.terminated.clone())
+        outputs = ("obs_internal", self._EXTERNAL[0], "reward", "terminated")
+        kept = {name: getattr(self, name).clone() for name in self._ROW_STATE + outputs}
+        for name in self._RESET_CLEARS:
+            setattr(self, name, torch.where(_over(mask, kept[name]), torch.zeros_like(kept[name]), kept[name]))
         self._launch(None)
-        self.state = torch.where(mask[:, None], self.state, others)
+        for name in self._ROW_STATE:
+            setattr(self, name, torch.where(_over(mask, kept[name]), getattr(self, name), kept[name]))
         self.state[:, 6] = torch.where(mask, torch.zeros_like(self.state[:, 6]), self.state[:, 6])
-        merged = self._merge(kept[0], self._obs(), mask)
-        self.obs_internal.copy_(merged["internal"]); self.obs_external.copy_(merged["external"])
-        self.reward.copy_(torch.where(mask, self.reward, kept[1]))
-        self.terminated.copy_(torch.where(mask, self.terminated, kept[2]))
+        for name in outputs:
+            getattr(self, name).copy_(torch.where(_over(mask, kept[name]), getattr(self, name), kept[name]))
         return self._obs()
 
+    def _saved(self) -> tuple:
+        return self._ROW_STATE + ("obs_internal", self._EXTERNAL[0], "reward", "terminated", "truncated")
+
     def state_dict(self) -> Dict:
-        """Everything a continuation needs: robot / clock state (incl. the one-step observation memory kept in it) and the
-        observation, reward and flags of the last launch."""
-        d = dict(state=self.state.clone(), obs_internal=self.obs_internal.clone(), obs_external=self.obs_external.clone(),
-                 reward=self.reward.clone(), terminated=self.terminated.clone(), truncated=self.truncated.clone())
+        """Everything a continuation needs: robot / clock state (incl. the one-step observation memory kept in it; the image
+        history of the image variant) and the observation, reward and flags of the last launch."""
+        d = {name: getattr(self, name).clone() for name in self._saved()}
         if self.records2 is not None:
             # maps change while the environment runs: both record tables (2 * B * R doubles, R = records.shape[1]; 16 * B * R
             # bytes) and the per-row vectors belong to the state
@@ -455,7 +455,7 @@ class BatchedRaysEnv:
     def load_state_dict(self, d: Dict) -> None:
         if ("records2" in d) != (self.records2 is not None):
             raise ValueError("state_dict and environment differ in enable_spares()")
-        for k in ("state", "obs_internal", "obs_external", "reward", "terminated", "truncated"):
+        for k in self._saved():
             getattr(self, k).copy_(d[k].to(self.device))
         if self.records2 is not None:
             for k in self._FRESH_KEYS:
@@ -477,26 +477,15 @@ class BatchedRaysEnv:
             terminated = self.terminated.bool()
             truncated = (self.state[:, 25] >= self.max_episode_steps) & ~terminated
             return obs, self.reward.clone(), terminated, truncated, {"success": (self.state[:, 7].to(torch.int64) & 4) != 0}
-        if self.records2 is not None:
-            if int(self.max_episode_steps) <= 0:
-                raise MpcGpuError("max_episode_steps must be positive")
-            self._fresh_launch(actions, int(self.max_episode_steps))
-            if getattr(self, "refill_every", 0):
-                self._calls += 1
-                if self._calls % self.refill_every == 0:
-                    self.refill()
-            return self._autoreset_result()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
-        if actions.shape != (self.B,):
-            raise ValueError(f"actions must have shape ({self.B},)")
-        rc = self._lib.mpcgpu_env_step_autoreset_dev(
-            self.device_index, C.byref(self.params), self.B, self.records.data_ptr(), self.state.data_ptr(),
-            actions.data_ptr(), self.obs_internal.data_ptr(), self.obs_external.data_ptr(), self.reward.data_ptr(),
-            self.terminated.data_ptr(), self.truncated.data_ptr(), self.term_internal.data_ptr(),
-            self.term_external.data_ptr(), int(self.max_episode_steps), stream)
-        if rc != 0:
-            raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
+        if int(self.max_episode_steps) <= 0:
+            # the library's own refusal of the auto-reset entry, in its words; made here because _launch, and the fresh entry
+            # itself, read max_steps = 0 as "no auto-reset"
+            raise MpcGpuError("max_episode_steps must be positive")
+        self._launch(actions, int(self.max_episode_steps))
+        if getattr(self, "refill_every", 0):     # behind the launch or launches of the step: see include/mpcgpu_map.h
+            self._calls += 1
+            if self._calls % self.refill_every == 0:
+                self.refill()
         return self._autoreset_result()
 
     def _autoreset_result(self):
@@ -504,15 +493,12 @@ class BatchedRaysEnv:
         obs = self._obs()
         terminated, truncated = self.terminated.bool(), self.truncated.bool()
         done = terminated | truncated
+        term_external = getattr(self, self._EXTERNAL[1])
         # state[7] already belongs to the next episode where a reset happened; state[26] keeps this step's flags
         info = {"success": (self.state[:, 26].to(torch.int64) & 4) != 0,
-                "terminal_observation": {"internal": torch.where(done[:, None], self.term_internal, obs["internal"]),
-                                         "external": torch.where(done[:, None], self.term_external, obs["external"])}}
+                "terminal_observation": {"internal": torch.where(_over(done, self.term_internal), self.term_internal, obs["internal"]),
+                                         "external": torch.where(_over(done, term_external), term_external, obs["external"])}}
         return obs, self.reward.clone(), terminated, truncated, info
-
-    def _merge(self, old, new, mask):
-        torch = self._torch
-        return {k: torch.where(mask[:, None], new[k], old[k]) for k in old}
 
     def set_agent_state(self, states) -> None:
         """``set_agent_state`` (environment.py:189-193) for every environment: rows of (x, y, theta, v, w)."""
@@ -638,132 +624,14 @@ class BatchedImgsEnv(BatchedRaysEnv):
             raise NotImplementedError(self._NO_TURNOVER)
         super().enable_fresh_maps(seed=seed, refill_every=refill_every)
 
-    def _fresh_launch(self, actions, max_steps: int) -> None:
-        torch = self._torch
-        aptr = None
-        if actions is not None:
-            actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
-            if actions.shape != (self.B,):
-                raise ValueError(f"actions must have shape ({self.B},)")
-            aptr = actions.data_ptr()
-        rc = self._lib.mpcgpu_env_step_imgs_fresh_dev(
-            self.device_index, C.byref(self.params), C.byref(self.img_params), self.B, self.records2.data_ptr(),
-            self.which.data_ptr(), self.spare_ready.data_ptr(), self.loaded.data_ptr(), self.stale.data_ptr(),
-            self.state.data_ptr(), self.img_state.data_ptr(), self.distance_field.data_ptr(), aptr,
-            self.obs_internal.data_ptr(), self.obs_image.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
-            self.truncated.data_ptr(), self.term_internal.data_ptr(), self.term_image.data_ptr(), int(max_steps),
-            torch.cuda.current_stream(self.device).cuda_stream)
-        if rc != 0:
-            raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
+    _EXTERNAL = ("obs_image", "term_image")
+    _ROW_STATE = ("state", "img_state")
+    _RESET_CLEARS = ("img_state",)               # the image history (environment.py:161-180)
+    _ENTRIES = ("mpcgpu_env_step_imgs_dev", "mpcgpu_env_step_imgs_autoreset_dev", "mpcgpu_env_step_imgs_fresh_dev")
 
-    def _launch(self, actions) -> None:
-        torch = self._torch
-        if self.records2 is not None:
-            return self._fresh_launch(actions, 0)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        aptr = None
-        if actions is not None:
-            actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
-            if actions.shape != (self.B,):
-                raise ValueError(f"actions must have shape ({self.B},)")
-            aptr = actions.data_ptr()
-        rc = self._lib.mpcgpu_env_step_imgs_dev(self.device_index, C.byref(self.params), C.byref(self.img_params), self.B,
-                                                self.records.data_ptr(), self.state.data_ptr(), self.img_state.data_ptr(),
-                                                self.distance_field.data_ptr(), aptr, self.obs_internal.data_ptr(),
-                                                self.obs_image.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
-                                                stream)
-        if rc != 0:
-            raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
-
-    def _obs(self) -> Dict[str, "object"]:
-        return {"internal": self.obs_internal.clone(), "external": self.obs_image.clone()}
-
-    def reset(self, mask=None):
-        """Reset all (or the masked) environments to their map's start state and clear their image history.  The launch
-        that observes the reset rows observes every row, so the other rows' state, image history, observation, reward and
-        flag are restored afterwards: a partial reset leaves them bit-identical."""
-        torch = self._torch
-        if mask is None:
-            mask = torch.ones(self.B, dtype=torch.bool, device=self.device)
-        mask = torch.as_tensor(mask, device=self.device).bool()
-        fresh = torch.zeros_like(self.state)
-        fresh[:, :5] = self._start if self.records2 is None else self.records2[self.which.long(), self._rows, 5:10]
-        fresh[:, 8:24] = self.state[:, 8:24]
-        self.state = torch.where(mask[:, None], fresh, self.state)
-        kept = (self.state.clone(), self.img_state.clone(), self.obs_internal.clone(), self.obs_image.clone(),
-                self.reward.clone(), self.terminated.clone())
-        self.img_state = torch.where(mask[:, None], torch.zeros_like(self.img_state), self.img_state)
-        self._launch(None)
-        self.state = torch.where(mask[:, None], self.state, kept[0])
-        self.state[:, 6] = torch.where(mask, torch.zeros_like(self.state[:, 6]), self.state[:, 6])
-        self.img_state = torch.where(mask[:, None], self.img_state, kept[1])
-        self.obs_internal.copy_(torch.where(mask[:, None], self.obs_internal, kept[2]))
-        self.obs_image.copy_(torch.where(mask[:, None, None, None], self.obs_image, kept[3]))
-        self.reward.copy_(torch.where(mask, self.reward, kept[4]))
-        self.terminated.copy_(torch.where(mask, self.terminated, kept[5]))
-        return self._obs()
-
-    def state_dict(self) -> Dict:
-        d = dict(state=self.state.clone(), img_state=self.img_state.clone(), obs_internal=self.obs_internal.clone(),
-                 obs_image=self.obs_image.clone(), reward=self.reward.clone(), terminated=self.terminated.clone(),
-                 truncated=self.truncated.clone())
-        if self.records2 is not None:            # both record tables and the per-row vectors, as BatchedRaysEnv.state_dict
-            d.update({k: getattr(self, k).clone() for k in self._FRESH_KEYS if getattr(self, k, None) is not None})
-            if getattr(self, "refill_every", 0):
-                d["refill_calls"] = self._calls
-        return d
-
-    def load_state_dict(self, d: Dict) -> None:
-        if ("records2" in d) != (self.records2 is not None):
-            raise ValueError("state_dict and environment differ in enable_spares()")
-        for k in ("state", "img_state", "obs_internal", "obs_image", "reward", "terminated", "truncated"):
-            getattr(self, k).copy_(d[k].to(self.device))
-        if self.records2 is not None:
-            for k in self._FRESH_KEYS:
-                if k in d and getattr(self, k, None) is not None:
-                    getattr(self, k).copy_(d[k].to(self.device))
-            if getattr(self, "refill_every", 0):
-                self._calls = int(d.get("refill_calls", 0))
-
-    def step(self, actions, auto_reset: bool = False):
-        """As :meth:`BatchedRaysEnv.step`; ``obs["external"]`` and ``info["terminal_observation"]["external"]`` are the
-        uint8 images."""
-        torch = self._torch
-        if not auto_reset:
-            self._launch(actions)
-            obs = self._obs()
-            terminated = self.terminated.bool()
-            truncated = (self.state[:, 25] >= self.max_episode_steps) & ~terminated
-            return obs, self.reward.clone(), terminated, truncated, {"success": (self.state[:, 7].to(torch.int64) & 4) != 0}
-        if self.records2 is not None:
-            if int(self.max_episode_steps) <= 0:
-                raise MpcGpuError("max_episode_steps must be positive")
-            self._fresh_launch(actions, int(self.max_episode_steps))
-            if getattr(self, "refill_every", 0):     # behind both launches of the step: see include/mpcgpu_map.h
-                self._calls += 1
-                if self._calls % self.refill_every == 0:
-                    self.refill()
-            return self._autoreset_result()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        actions = torch.as_tensor(actions, device=self.device).to(torch.int32).contiguous()
-        if actions.shape != (self.B,):
-            raise ValueError(f"actions must have shape ({self.B},)")
-        rc = self._lib.mpcgpu_env_step_imgs_autoreset_dev(
-            self.device_index, C.byref(self.params), C.byref(self.img_params), self.B, self.records.data_ptr(),
-            self.state.data_ptr(), self.img_state.data_ptr(), self.distance_field.data_ptr(), actions.data_ptr(),
-            self.obs_internal.data_ptr(), self.obs_image.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
-            self.truncated.data_ptr(), self.term_internal.data_ptr(), self.term_image.data_ptr(),
-            int(self.max_episode_steps), stream)
-        if rc != 0:
-            raise MpcGpuError(self._lib.mpcgpu_env_last_error().decode())
-        return self._autoreset_result()
-
-    def _autoreset_result(self):
-        torch = self._torch
-        obs = self._obs()
-        terminated, truncated = self.terminated.bool(), self.truncated.bool()
-        done = terminated | truncated
-        info = {"success": (self.state[:, 26].to(torch.int64) & 4) != 0,
-                "terminal_observation": {"internal": torch.where(done[:, None], self.term_internal, obs["internal"]),
-                                         "external": torch.where(done[:, None, None, None], self.term_image, obs["external"])}}
-        return obs, self.reward.clone(), terminated, truncated, info
+    def _args(self, table: tuple, aptr, max_steps) -> tuple:
+        tail = () if max_steps is None else (self.truncated.data_ptr(), self.term_internal.data_ptr(),
+                                             self.term_image.data_ptr(), max_steps)
+        return (self.device_index, C.byref(self.params), C.byref(self.img_params), self.B, *table, self.state.data_ptr(),
+                self.img_state.data_ptr(), self.distance_field.data_ptr(), aptr, self.obs_internal.data_ptr(),
+                self.obs_image.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(), *tail)

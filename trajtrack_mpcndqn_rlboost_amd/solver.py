@@ -203,6 +203,25 @@ def load_library(path: Optional[str] = None):
     return L
 
 
+def bind_exports(lib, tag: str, table, sources: str):
+    """Signatures of a side module's exports (environment, map stream, planner, replay tree, fleet) on the handle ``lib``:
+    ``table`` is ``{export name: (restype, argtypes)}``, ``sources`` the files to rebuild when an export is missing.  Done
+    once per handle and ``tag``; returns ``lib``."""
+    bound = getattr(lib, "_bound_tags", None)
+    if bound is None:
+        bound = lib._bound_tags = set()
+    if tag in bound:
+        return lib
+    missing = [name for name in table if not hasattr(lib, name)]
+    if missing:
+        raise MpcGpuError(f"libmpcgpu.so lacks {missing}: rebuild it ({sources}); there is no fallback")
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
+    bound.add(tag)
+    return lib
+
+
 @dataclass
 class BatchResult:
     """Per-problem fields of the OpEn solution object (``solution, cost, exit_status, solve_time_ms`` are the
