@@ -1,0 +1,131 @@
+"""Parameters and minibatches for the tests of the fused DQN update (tests/test_dqn_fused_host.py, tests/test_gpu_dqn_fused.py):
+random ones and the edge cases the kernel's branches have -- ties of the arg-max, terminal rows, a dead hidden layer, the kinks
+of the Huber loss, an active and an idle gradient clip, the first, last and out-of-range actions."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import dqn_numpy as tw
+
+F = np.float32
+SIZES = (1, 2, 31, 32, 33, 63, 64, 65, 255, 256)
+
+
+def random_theta(rng) -> np.ndarray:
+    """torch's default Linear initialisation: uniform in +- 1 / sqrt(fan_in)."""
+    theta = np.zeros(tw.NP, F)
+    for part, fan_in in zip(tw.split(theta), (46, 46, 16, 16, 16, 16)):
+        part[...] = rng.uniform(-1.0, 1.0, part.shape) / np.sqrt(fan_in)
+    return theta
+
+
+def random_batch(rng, n: int, weights: bool = False, reward_scale: float = 1.0) -> dict:
+    b = dict(obs=rng.uniform(-1.0, 1.0, (n, 46)).astype(F), next_obs=rng.uniform(-1.0, 1.0, (n, 46)).astype(F),
+             actions=rng.integers(0, 9, n).astype(np.int64), rewards=(reward_scale * rng.standard_normal(n)).astype(F),
+             dones=(rng.random(n) < 0.25).astype(F))
+    if weights:
+        b["weights"] = rng.uniform(0.05, 1.0, n).astype(F)
+    return b
+
+
+def kink_batch(rng, theta, n: int) -> dict:
+    """Terminal rows (y = r) whose reward puts delta = r - q[a] on a kink of the Huber loss, one float32 inside and one outside
+    of it, on both sides: row i takes case i mod 6 of (+1, -1, +inside, +outside, -inside, -outside)."""
+    b = random_batch(rng, n)
+    b["dones"][:] = 1.0
+    qa = tw.network(theta, b["obs"])[2][np.arange(n), b["actions"]]
+    inside, outside = np.nextafter(F(1), F(0)), np.nextafter(F(1), F(2))
+    for i in range(n):
+        sign, want = ((1, F(1)), (-1, F(1)), (1, inside), (1, outside), (-1, inside), (-1, outside))[i % 6]
+        r = F(qa[i] + F(sign) * want)
+        cands = [r]
+        for direction in (F(-np.inf), F(np.inf)):
+            c = r
+            for _ in range(4):
+                c = np.nextafter(c, direction)
+                cands.append(c)
+        err = [abs(float(abs(F(c - qa[i]))) - float(want)) for c in cands]
+        b["rewards"][i] = cands[int(np.argmin(err))]
+    return b
+
+
+def kink_census(delta) -> dict:
+    """How many rows of ``delta`` sit exactly on each of the six cases of :func:`kink_batch`."""
+    inside, outside = np.nextafter(F(1), F(0)), np.nextafter(F(1), F(2))
+    return {"+1": int(np.sum(delta == 1)), "-1": int(np.sum(delta == -1)), "+in": int(np.sum(delta == inside)),
+            "+out": int(np.sum(delta == outside)), "-in": int(np.sum(delta == -inside)), "-out": int(np.sum(delta == -outside))}
+
+
+def edge_cases(seed: int = 11, n: int = 33) -> dict:
+    """name -> dict(theta, target, batch, double_q)."""
+    rng = np.random.default_rng(seed)
+    cases = {}
+
+    def case(name, theta=None, target=None, double_q=False, **kw):
+        theta = random_theta(rng) if theta is None else theta
+        target = random_theta(rng) if target is None else target
+        cases[name] = dict(theta=theta, target=target, batch=kw.pop("batch", None) or random_batch(rng, n, **kw), double_q=double_q)
+        return cases[name]
+
+    case("plain")
+    case("weights", weights=True)
+    case("double_q", double_q=True)
+    # exact ties of the online arg-max on next_obs: output rows 1, 3 and 5 are copies and carry the largest bias, so every row
+    # ties between them; the target network values them differently, so the index chosen shows in next_v
+    tied = random_theta(rng)
+    W2, b2 = tw.split(tied)[4:]
+    W2[3], W2[5] = W2[1], W2[1]
+    b2[[1, 3, 5]] = 5.0
+    case("double_q_ties", theta=tied, double_q=True)
+    case("max_ties", target=tied.copy())
+    c = case("all_done")
+    c["batch"]["dones"][:] = 1.0
+    dead = random_theta(rng)
+    tw.split(dead)[3][:] = -100.0          # b1: no unit of the second hidden layer fires
+    case("dead_hidden", theta=dead)
+    dead0 = random_theta(rng)
+    tw.split(dead0)[1][:] = -100.0         # b0: no unit of the first hidden layer fires
+    case("dead_first_hidden", theta=dead0, weights=True)
+    kt = random_theta(rng)
+    case("kinks", theta=kt, batch=kink_batch(rng, kt, max(n, 36)))
+    # every row's coefficient is bounded by the Huber loss, so large rewards alone do not reach a norm of 10: the observations
+    # of this case are large as well (the gradient of W0 grows with them)
+    c = case("rewards_1e3", reward_scale=1e3)
+    c["batch"]["obs"] *= F(400.0)
+    case("rewards_1e-3", reward_scale=1e-3)
+    c = case("actions_edge")
+    c["batch"]["actions"][:] = np.resize(np.array([0, 8, -1, 9], np.int64), n)
+    return cases
+
+
+def torch_trainer(theta, target, double_q=False, dtype=None, device="cpu", **kw):
+    """``dqn_train.DqnTrainer`` holding the flat parameter vectors ``theta`` / ``target`` (``dtype``: torch.float64 for the
+    yardstick of the gradient tests)."""
+    import torch
+    from trajtrack_mpcndqn_rlboost_amd import dqn, dqn_train
+    dtype = dtype or torch.float32
+    net = dqn.QNetwork().to(dtype)
+    tr = dqn_train.DqnTrainer(q_net=net, double_q=double_q, device=device, **kw)
+    for module, flat in ((tr.q_net, theta), (tr.q_net_target, target)):
+        off = 0
+        with torch.no_grad():
+            for p in module.parameters():
+                p.copy_(torch.from_numpy(np.asarray(flat[off:off + p.numel()], np.float64)).reshape(p.shape).to(dtype))
+                off += p.numel()
+    return tr
+
+
+def torch_batch(batch, dtype=None, device="cpu"):
+    """The batch as torch tensors, actions clamped into 0..8 (the kernel's rule for an index out of range)."""
+    import torch
+    dtype = dtype or torch.float32
+    out = {k: torch.from_numpy(v).to(device=device, dtype=dtype) for k, v in batch.items() if k != "actions"}
+    out["actions"] = torch.from_numpy(np.clip(batch["actions"], 0, 8)).to(device)
+    return out
+
+
+def torch_gradient(theta, target, batch, double_q=False, dtype=None, device="cpu"):
+    """Flat gradient of the trainer's own loss by autograd, as float64 numpy."""
+    tr = torch_trainer(theta, target, double_q, dtype, device)
+    tr._backward(torch_batch(batch, dtype, device))
+    return np.concatenate([p.grad.detach().double().cpu().numpy().reshape(-1) for p in tr.q_net.parameters()])

@@ -1,0 +1,207 @@
+"""The fused DQN update without a GPU: the binding table of ``dqn_fused``, the numpy twin of csrc/dqngpu.hip
+(tests/support/dqn_numpy.py) against float64 evaluations of the same step, its sampler against Python integers, the refusals
+of ``DqnLearner(fused=True)`` and ``FusedDqnTrainer``, and Adam's ``state_dict`` between the two trainers."""
+import ctypes as C
+import importlib
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from support import dqn_cases, dqn_numpy as tw
+from trajtrack_mpcndqn_rlboost_amd import dqn, dqn_fused, dqn_train, map_stream
+
+solver_mod = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.solver")
+F = np.float32
+ARGUMENTS = {"mpcgpu_dqn_state_floats": 0, "mpcgpu_dqn_grad_dev": 14, "mpcgpu_dqn_apply_dev": 6, "mpcgpu_dqn_step_dev": 14,
+             "mpcgpu_dqn_train_dev": 15, "mpcgpu_dqn_last_error": 0}
+
+
+# ---- binding ---------------------------------------------------------------------------------------------------------------
+def test_export_tuple_is_the_key_tuple_of_the_table():
+    assert isinstance(dqn_fused.DQN_EXPORTS, tuple) and dqn_fused.DQN_EXPORTS == tuple(dqn_fused._DQN_TABLE)
+    assert set(dqn_fused.DQN_EXPORTS) == set(ARGUMENTS)
+    for name, (restype, argtypes) in dqn_fused._DQN_TABLE.items():
+        assert len(argtypes) == ARGUMENTS[name], name
+        assert restype is (C.c_char_p if name.endswith("_last_error") else C.c_int32), name
+
+
+def test_a_library_that_lacks_an_export_is_refused_by_name():
+    exports = dqn_fused.DQN_EXPORTS
+    for gone in exports:
+        stand_in = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in exports if e != gone})
+        with pytest.raises(solver_mod.MpcGpuError) as err:
+            dqn_fused._bind(stand_in)
+        text = str(err.value)
+        assert gone in text and "csrc/dqngpu.hip" in text and "rebuild" in text and "no fallback" in text
+        assert not any(hasattr(fn, "argtypes") for fn in vars(stand_in).values())      # refused before anything was set
+    whole = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in exports})
+    assert dqn_fused._bind(whole) is whole and len(whole.mpcgpu_dqn_train_dev.argtypes) == 15
+
+
+def test_the_built_library_has_the_exports_and_the_state_layout():
+    lib = dqn_fused._bind(solver_mod.load_library())
+    assert lib.mpcgpu_dqn_state_floats() == tw.STATE_FLOATS == 4 * tw.NP + 4 and dqn_fused.STATE_T == tw.STATE_T
+    assert sum(int(np.prod(s)) for s in dqn_fused.SHAPES) == tw.NP == sum(p.numel() for p in dqn.QNetwork().parameters())
+    assert tuple(tuple(p.shape) for p in dqn.QNetwork().parameters()) == dqn_fused.SHAPES
+
+
+# ---- the twin's gradient against float64 autograd ---------------------------------------------------------------------------
+def gradient_errors(case):
+    """(E, the twin's deviation): maximum absolute deviations of the eager float32 torch gradient and of the twin's gradient
+    from float64 autograd of the same loss on the same inputs."""
+    args = (case["theta"], case["target"], case["batch"], case["double_q"])
+    exact = dqn_cases.torch_gradient(*args, dtype=torch.float64)
+    eager = dqn_cases.torch_gradient(*args, dtype=torch.float32)
+    b = case["batch"]
+    mine = tw.gradient(case["theta"], case["target"], b["obs"], b["next_obs"], b["actions"], b["rewards"], b["dones"],
+                       b.get("weights"), 0.98, case["double_q"])[0]
+    return float(np.abs(eager - exact).max()), float(np.abs(mine.astype(np.float64) - exact).max())
+
+
+EDGE = dqn_cases.edge_cases()
+
+
+@pytest.mark.parametrize("name", sorted(EDGE))
+def test_twin_gradient_on_the_edge_batches(name):
+    E, mine = gradient_errors(EDGE[name])
+    print(f"{name}: eager float32 off by E = {E:.3e}, twin by {mine:.3e} (ratio {mine / E if E else float('nan'):.2f})")
+    assert mine <= 4.0 * E
+
+
+@pytest.mark.parametrize("n", [1, 32, 65, 256])
+def test_twin_gradient_on_random_batches(n):
+    rng = np.random.default_rng(500 + n)
+    for k in range(3):
+        case = dict(theta=dqn_cases.random_theta(rng), target=dqn_cases.random_theta(rng),
+                    batch=dqn_cases.random_batch(rng, n, weights=k == 1), double_q=k == 2)
+        E, mine = gradient_errors(case)
+        print(f"n = {n}, batch {k}: E = {E:.3e}, twin {mine:.3e} (ratio {mine / E if E else float('nan'):.2f})")
+        assert mine <= 4.0 * E
+
+
+def test_the_edge_batches_are_what_they_claim():
+    def run(name):
+        c, b = EDGE[name], EDGE[name]["batch"]
+        return tw.gradient(c["theta"], c["target"], b["obs"], b["next_obs"], b["actions"], b["rewards"], b["dones"],
+                           b.get("weights"), 0.98, c["double_q"])
+    census = dqn_cases.kink_census(run("kinks")[2])
+    assert min(census.values()) >= 1, census
+    g = run("dead_hidden")[0]
+    assert not g[:tw.OFF_W2].any() and g[tw.OFF_B2:].any()            # nothing reaches below the dead layer
+    c = EDGE["double_q_ties"]
+    qo = tw.network(c["theta"], c["batch"]["next_obs"])[2]
+    assert np.all(qo[:, 1] == qo.max(axis=1)) and np.all(qo[:, 1] == qo[:, 3]) and np.all(qo[:, 3] == qo[:, 5])
+    qt = tw.network(c["target"], c["batch"]["next_obs"])[2]
+    assert np.any(qt[:, 1] != qt[:, 3])
+    norm = lambda name: float(np.sqrt(np.sum(run(name)[0].astype(np.float64) ** 2)))
+    assert norm("rewards_1e3") > 10.0 > norm("rewards_1e-3")          # the clip is active / is not
+    assert set(EDGE["actions_edge"]["batch"]["actions"].tolist()) == {0, 8, -1, 9}
+
+
+# ---- the twin's Adam step against float64, given the same gradient -----------------------------------------------------------
+def adam_float64(theta, m, v, t, g, lr=1e-4, max_norm=10.0, b1=0.9, b2=0.999, eps=1e-8):
+    theta, m, v, g = (np.asarray(x, np.float64) for x in (theta, m, v, g))
+    g = g * min(1.0, max_norm / (np.sqrt(np.sum(g * g)) + 1e-6))
+    t = t + 1
+    m = b1 * m + (1 - b1) * g
+    v = b2 * v + (1 - b2) * g * g
+    u = (lr / (1 - b1 ** t)) * m / (np.sqrt(v) / np.sqrt(1 - b2 ** t) + eps)
+    return theta - u, u
+
+
+@pytest.mark.parametrize("t", [0, 1, 999, 10 ** 6])
+@pytest.mark.parametrize("gscale", [0.0, 1e-4, 1.0, 1e3])
+def test_twin_adam_step(t, gscale):
+    rng = np.random.default_rng(7 + t % 1000)
+    theta = dqn_cases.random_theta(rng)
+    g = (gscale * rng.standard_normal(tw.NP)).astype(F)
+    g[::7] = 0.0
+    fresh = t == 0
+    m = np.zeros(tw.NP, F) if fresh else (0.1 * rng.standard_normal(tw.NP)).astype(F)
+    v = np.zeros(tw.NP, F) if fresh else (rng.random(tw.NP) ** 4).astype(F)
+    if not fresh:
+        m[::7], v[::7] = 0.0, 0.0          # with g = 0 there: 0 / (0 + eps)
+    new, m1, v1, t1 = tw.apply(theta, m, v, t, g)
+    exact, u = adam_float64(theta, m, v, t, g)
+    assert t1 == t + 1 and new.dtype == m1.dtype == v1.dtype == F
+    assert np.array_equal(new[::7], theta[::7])
+    bound = 2.0 ** -23 * (np.abs(theta.astype(np.float64)) + 8.0 * np.abs(u))
+    worst = float(np.max(np.abs(new.astype(np.float64) - exact) / bound))
+    print(f"t = {t}, |g| ~ {gscale:g}: worst |d theta| / bound = {worst:.3f}")
+    assert worst <= 1.0
+
+
+# ---- sampling ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("size", [1, 2, 3, 2 ** 31 - 1, 10 ** 6])
+def test_sampled_rows_are_python_integer_arithmetic_on_the_map_stream(size):
+    for seed, serial in ((0, 0), (12345, 7), (2 ** 64 - 1, 2 ** 40 + 3)):
+        stream = map_stream.CounterUniform(seed, serial)              # the host twin of the stream of include/mpcgpu_map.h
+        want = [(stream.bits(i) * size) >> 64 for i in range(256)]
+        rows = tw.sample_rows(seed, serial, 256, size)
+        assert rows.tolist() == want and 0 <= min(want) and max(want) < size
+    if size > 2:
+        assert len(set(tw.sample_rows(1, 1, 256, size).tolist())) > 2
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------
+def _env(image):
+    return types.SimpleNamespace(B=4, device=torch.device("cpu"), is_image_env=image, image_shape=(3, 54, 54))
+
+
+def test_fused_learner_refuses_an_image_environment():
+    with pytest.raises(ValueError, match="fused=True.*ray"):
+        dqn_train.DqnLearner(_env(True), fused=True, buffer_size=8)
+
+
+def test_fused_learner_refuses_use_graph():
+    with pytest.raises(ValueError, match="fused=True and use_graph=True"):
+        dqn_train.DqnLearner(_env(False), fused=True, use_graph=True, buffer_size=8)
+
+
+def test_fused_learner_refuses_another_trainer():
+    with pytest.raises(ValueError, match="FusedDqnTrainer"):
+        dqn_train.DqnLearner(_env(False), trainer=dqn_train.DqnTrainer(), fused=True, buffer_size=8)
+
+
+def test_fused_trainer_refuses_a_process_without_a_hip_device():
+    with pytest.raises(solver_mod.MpcGpuError, match="needs a HIP device"):
+        dqn_fused.FusedDqnTrainer(device="cpu")
+    if not torch.cuda.is_available():
+        with pytest.raises(solver_mod.MpcGpuError, match="needs a HIP device"):
+            dqn_fused.FusedDqnTrainer(device="cuda")
+
+
+def test_fused_trainer_refuses_a_network_of_another_shape():
+    with pytest.raises(ValueError, match="QNetwork's shape"):
+        dqn_fused.FusedDqnTrainer(q_net=dqn.QNetwork(hidden=(32, 32)), device="cpu")
+
+
+# ---- Adam's state_dict between the two trainers ---------------------------------------------------------------------------------
+def test_adam_state_dict_round_trips_between_the_trainers():
+    rng = np.random.default_rng(3)
+    theta, target = dqn_cases.random_theta(rng), dqn_cases.random_theta(rng)
+    batches = [dqn_cases.torch_batch(dqn_cases.random_batch(rng, 32)) for _ in range(4)]
+    a = dqn_cases.torch_trainer(theta, target)
+    for b in batches[:3]:
+        a.update(b)
+    sd = a.optimizer.state_dict()
+    m, v, t = dqn_fused.adam_state_of(sd)                            # DqnTrainer -> the fused trainer's block
+    assert t == 3 and m.shape == v.shape == (tw.NP,) and m.dtype == torch.float32
+    flat = lambda key: torch.cat([sd["state"][i][key].reshape(-1) for i in range(6)])
+    assert torch.equal(m, flat("exp_avg")) and torch.equal(v, flat("exp_avg_sq"))
+    back = dqn_fused.adam_state_dict(m, v, t, dqn_fused.adam_groups(1e-4))       # ... and back into a DqnTrainer
+    assert set(back["param_groups"][0]) == set(sd["param_groups"][0])
+    b = dqn_cases.torch_trainer(theta, target)
+    b.q_net.load_state_dict(a.q_net.state_dict())
+    b.load_optimizer_state(back)
+    a.update(batches[3]); b.update(batches[3])
+    for pa, pb in zip(a.q_net.parameters(), b.q_net.parameters()):
+        assert torch.equal(pa, pb)
+    assert dqn_fused.adam_state_of(b.optimizer.state_dict())[2] == 4
+    assert dqn_fused.adam_state_of(dqn_cases.torch_trainer(theta, target).optimizer.state_dict())[2] == 0     # never stepped
+    with pytest.raises(ValueError, match="step counts"):
+        broken = a.optimizer.state_dict()
+        broken["state"][2]["step"] = torch.tensor(9.0)
+        dqn_fused.adam_state_of(broken)

@@ -3,10 +3,14 @@
 
     python tools/train_dqn.py [--gpus N] [--envs 4096] [--timesteps 4000000] [--gradient-steps 16] [--batch-size 256]
                               [--save DIR] [--resume DIR/checkpoint.pt] [--checkpoint-every STEPS]
-                              [--images] [--fresh-maps] [--per] [--buffer-size N]
+                              [--images] [--fresh-maps] [--per] [--buffer-size N] [--graph | --fused]
 
 `--images` trains dqn.ImageQNetwork on the image environment (rl_env.BatchedImgsEnv); with `--fresh-maps` every episode of it
 starts on a new random map too (map_turnover=True, capacity map_stream.DYNAMIC_CAPACITY, stream seed + rank).
+
+`--fused` runs the update as the fused HIP kernel (dqn_fused.FusedDqnTrainer; ray network, batch size at most
+256): with uniform replay and one rank a whole update round is one launch, which makes `--gradient-steps -1` -- one gradient
+step per collected transition, the reference's setting -- affordable.
 
 `--save DIR` writes what the reference's run leaves behind (src/test_block_rl.py:73-76,89-96: EvalCallback's best_model and
 model.save's final_model) -- best_model.pt whenever the mean return of a progress window improves, final_model.pt at the end --
@@ -88,6 +92,8 @@ def main():
     ap.add_argument("--double-q", action="store_true")
     ap.add_argument("--per", action="store_true", help="prioritized experience replay (device-resident sum tree; the reference's 'per': True)")
     ap.add_argument("--graph", action="store_true", help="replay the update from captured HIP graphs (multi-rank: two graphs around the all-reduce)")
+    ap.add_argument("--fused", action="store_true",
+                    help="the update as one fused HIP kernel (ray network only); with it --gradient-steps -1 is the reference's ratio")
     ap.add_argument("--save", default=None, help="directory for best_model.pt / final_model.pt / checkpoint.pt")
     ap.add_argument("--resume", default=None, help="checkpoint.pt of an earlier run with the same arguments")
     ap.add_argument("--checkpoint-every", type=int, default=0, help="environment steps between checkpoints (0: only at the end)")
@@ -121,13 +127,19 @@ def main():
             [scene(rng) for _ in range(args.envs)], device=local, max_episode_steps=400)
     if args.images and args.graph:
         sys.exit("train_dqn.py: --graph is not built for --images (the image update runs eagerly)")
+    if args.fused and (args.images or args.graph):
+        sys.exit("train_dqn.py: --fused is built for the ray network and excludes --graph")
     q_net = dqn_train.ImageQNetwork(env.image_shape) if args.images else None
-    trainer = dqn_train.DqnTrainer(q_net=q_net, device=f"cuda:{local}", double_q=args.double_q, lr=1e-3)
+    if args.fused:
+        trainer = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.dqn_fused").FusedDqnTrainer(
+            device=f"cuda:{local}", double_q=args.double_q, lr=1e-3)
+    else:
+        trainer = dqn_train.DqnTrainer(q_net=q_net, device=f"cuda:{local}", double_q=args.double_q, lr=1e-3)
     buffer_size = args.buffer_size or (200_000 if args.images else 2_000_000)
     learner = dqn_train.DqnLearner(env, trainer, buffer_size=buffer_size, learning_starts=4 * args.envs,
                                    batch_size=args.batch_size, train_freq=4, gradient_steps=args.gradient_steps,
                                    target_update_interval=200_000, exploration_fraction=0.3, use_graph=args.graph,
-                                   track_episodes=False, per=args.per)
+                                   track_episodes=False, per=args.per, fused=args.fused)
     ck_name = "checkpoint.pt" if rank == 0 else f"checkpoint.rank{rank}.pt"
     if args.resume:
         learner.load(args.resume if rank == 0 else os.path.join(os.path.dirname(args.resume), ck_name))
@@ -172,7 +184,9 @@ def main():
                           "value": world * stats["timesteps"] / dt, "unit": "environment steps/s", "n_gpus": world,
                           "rccl_ranks": dist.get_world_size() if world > 1 else 1, "backend": "nccl" if world > 1 else None,
                           "updates_per_s": stats["updates"] / dt, "gradient_all_reduce_floats": 1177 if world > 1 else 0,
-                          "update_path": "two HIP graphs around one flat RCCL all-reduce" if (args.graph and world > 1) else
+                          "update_path": ("fused HIP kernels around one flat RCCL all-reduce" if world > 1 else
+                                          "fused HIP kernel, one launch per step" if args.per else
+                                          "fused HIP kernel, one launch per update round") if args.fused else "two HIP graphs around one flat RCCL all-reduce" if (args.graph and world > 1) else
                                          ("one HIP graph" if args.graph else "eager"),
                           "config": {"workload": "BASELINE.json config 5 (scene 1, medium box, periodic obstacle)",
                                      "envs_per_gpu": args.envs, "timesteps_per_gpu": int(stats["timesteps"]),

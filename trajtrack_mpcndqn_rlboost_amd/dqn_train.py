@@ -405,16 +405,34 @@ class DqnLearner:
                  target_update_interval: int = 10_000, exploration_fraction: float = 0.2,
                  exploration_initial_eps: float = 1.0, exploration_final_eps: float = 0.05, seed: int = 0,
                  use_graph: bool = False, track_episodes: bool = True, per: bool = False,
-                 per_kwargs: Optional[Dict] = None):
+                 per_kwargs: Optional[Dict] = None, fused: bool = False):
         """``per=True``: prioritized experience replay (the reference's ``'per': True``): the buffer keeps a sum tree of
         priorities (``per_kwargs``: alpha, beta, epsilon, update_max_freq, initial_priority), minibatches are drawn by
         priority, the loss is weighted by the importance weights and the drawn rows are re-prioritized with their TD errors
-        after every update -- all on the device.  With several ranks every rank has its own tree."""
+        after every update -- all on the device.  With several ranks every rank has its own tree.
+
+        ``fused=True`` (ray environment only): the update is the fused HIP kernel of :class:`dqn_fused.FusedDqnTrainer`
+        (DESIGN.md 8.6).  With uniform replay and one rank the whole update round of ``learn`` is ONE launch that draws its
+        own minibatches from the counter stream ``(seed + rank, serial)`` -- both are part of ``state_dict`` --; with
+        ``per=True`` or several ranks it is one fused update per step around the tree's kernels or the all-reduce."""
         self.env = env
         self.device = env.device
         self.image = bool(getattr(env, "is_image_env", False))
         if self.image and use_graph:
             raise ValueError("use_graph=True is not built for the image environment: its updates run eagerly")
+        self.fused = bool(fused)
+        if self.fused and self.image:
+            raise ValueError("fused=True is built for the ray Q-network only: the image environment's updates run eagerly")
+        if self.fused and use_graph:
+            raise ValueError("fused=True and use_graph=True exclude each other: the fused update is one launch already")
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        if self.fused:
+            from .dqn_fused import FusedDqnTrainer
+            if trainer is None:
+                trainer = FusedDqnTrainer(device=str(self.device))
+            elif not isinstance(trainer, FusedDqnTrainer):
+                raise ValueError("fused=True needs a dqn_fused.FusedDqnTrainer")
+            trainer.seed, trainer.serial = seed + rank, 0
         if trainer is None:
             q_net = ImageQNetwork(env.image_shape) if self.image else None
             trainer = DqnTrainer(q_net=q_net, device=str(self.device))
@@ -475,6 +493,8 @@ class DqnLearner:
                  ep_return_sum=self.ep_return_sum.clone(), ep_success_sum=self.ep_success_sum.clone(),
                  obs=None if self._obs is None else _clone_obs(self._obs),
                  ep_return=None if self._ep_return is None else self._ep_return.clone())
+        if self.fused:
+            d["fused_seed"], d["fused_serial"] = tr.seed, tr.serial
         if include_buffer and (self.image or self.per):
             d["buffer"] = self.buffer.state_dict()
         elif include_buffer:
@@ -490,6 +510,8 @@ class DqnLearner:
         tr.q_net.load_state_dict(d["q_net"]); tr.q_net_target.load_state_dict(d["q_net_target"])
         tr.load_optimizer_state(d["optimizer"])     # in place when the update has been captured into a graph
         tr.num_updates, tr.num_target_syncs = d["num_updates"], d["num_target_syncs"]
+        if self.fused:
+            tr.seed, tr.serial = d["fused_seed"], d["fused_serial"]
         self.num_timesteps, self.n_calls, self.n_updates = d["num_timesteps"], d["n_calls"], d["n_updates"]
         self.gen.set_state(d["generator"].cpu())   # a generator state is a host ByteTensor, also for a device generator
         self.episode_returns, self.episode_successes = list(d["episode_returns"]), list(d["episode_successes"])
@@ -569,7 +591,11 @@ class DqnLearner:
                     break
             if self.num_timesteps > self.learning_starts and self.buffer.size >= self.batch_size:
                 steps = self.gradient_steps if self.gradient_steps >= 0 else collected
-                for _ in range(steps):
+                # fused, uniform replay, one rank: the whole round is one launch that samples the buffer itself
+                one_launch = self.fused and not self.per and not self.trainer._collective
+                if one_launch and steps > 0:
+                    last_loss = self.trainer.train(self.buffer, steps, self.batch_size)[-1]
+                for _ in range(0 if one_launch else steps):
                     step = self.trainer.update_graphed if self.use_graph else self.trainer.update
                     batch = self.buffer.sample(self.batch_size, self.gen)
                     last_loss = step(batch)
