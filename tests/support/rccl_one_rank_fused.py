@@ -34,7 +34,7 @@ def main():
         single = dqn_fused.FusedDqnTrainer(device=dev, target_update_interval=4)
         torch.manual_seed(0)
         coll = dqn_fused.FusedDqnTrainer(device=dev, target_update_interval=4, force_collective=True)
-        assert coll._collective and not single._collective and torch.equal(single.state, coll.state)
+        assert coll.collective and not single.collective and torch.equal(single.state, coll.state)
         for b in batches:
             la, lb = single.update(b), coll.update(b)
             assert torch.equal(la, lb) and torch.equal(single.last_td_error, coll.last_td_error)

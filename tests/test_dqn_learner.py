@@ -65,6 +65,66 @@ def test_replay_buffer_wraps_and_samples_stored_rows():
     assert torch.equal(s["actions"].float(), s["obs"][:, 0])
 
 
+def _image_rows(k, n=4):
+    img, internal = torch.full((n, 3, 9, 11), k, dtype=torch.uint8), torch.full((n, 14), float(k))
+    return {"external": img, "internal": internal}, {"external": img + 100, "internal": internal + 0.5}
+
+
+def _filled(image, adds, capacity=10):
+    """``adds`` times four rows whose every entry encodes the number of the add."""
+    cpu = torch.device("cpu")
+    buf = dqn_train.ImageReplayBuffer(capacity, (3, 9, 11), 14, cpu) if image else dqn_train.ReplayBuffer(capacity, 46, cpu)
+    for k in range(adds):
+        o, nxt = _image_rows(k) if image else (torch.full((4, 46), float(k)), torch.full((4, 46), k + 0.5))
+        buf.add(o, nxt, torch.full((4,), k), torch.full((4,), -float(k)), torch.full((4,), float(k % 2)))
+    return buf
+
+
+def test_image_replay_buffer_wraps_and_samples_stored_rows():
+    buf = _filled(True, 4)
+    assert buf.size == 10 and buf.pos == 6 and buf.capacity == 10 and buf.sum_tree is None
+    assert buf.img.dtype == buf.next_img.dtype == torch.uint8 and buf.img.shape == buf.next_img.shape == (10, 3, 9, 11)
+    assert buf.internal.shape == buf.next_internal.shape == (10, 14) and buf.internal.dtype == torch.float32
+    assert sorted(buf.img[:, 0, 0, 0].tolist()) == [1, 1, 2, 2, 2, 2, 3, 3, 3, 3]
+    s = buf.sample(64, torch.Generator().manual_seed(1))
+    assert list(s) == ["obs", "actions", "rewards", "next_obs", "dones"]
+    k = s["obs"]["internal"][:, 0]
+    assert len(set(k.tolist())) == 3 and s["obs"]["external"].dtype == torch.uint8
+    assert torch.equal(s["obs"]["external"], k.to(torch.uint8)[:, None, None, None].expand(-1, 3, 9, 11))
+    assert torch.equal(s["obs"]["internal"], k[:, None].expand(-1, 14))
+    assert torch.equal(s["next_obs"]["external"], s["obs"]["external"] + 100)
+    assert torch.equal(s["next_obs"]["internal"], s["obs"]["internal"] + 0.5)
+    assert torch.equal(s["rewards"], -k) and torch.equal(s["actions"].float(), k) and torch.equal(s["dones"], k % 2)
+    # the rows drawn are those of ONE torch.randint call on the generator
+    idx = torch.randint(0, 10, (64,), generator=torch.Generator().manual_seed(1))
+    assert torch.equal(s["obs"]["external"], buf.img[idx]) and torch.equal(s["next_obs"]["internal"], buf.next_internal[idx])
+
+
+@pytest.mark.parametrize("image", [False, True])
+@pytest.mark.parametrize("adds", [1, 4])
+def test_replay_buffers_round_trip_through_their_state_dict(image, adds):
+    """size < capacity (one add) and after a wrap (four adds of four rows into ten)."""
+    buf = _filled(image, adds)
+    n = buf.size
+    assert (n, buf.pos) == ((4, 4) if adds == 1 else (10, 6))
+    sd = buf.state_dict()
+    assert list(sd) == ["pos", "size"] + list(buf.FIELDS) and (sd["pos"], sd["size"]) == (buf.pos, n)
+    assert buf.FIELDS == (("img", "next_img", "internal", "next_internal") if image else ("obs", "next_obs")) + ("actions", "rewards", "dones")
+    assert all(sd[k].shape[0] == n and sd[k].data_ptr() != getattr(buf, k).data_ptr() for k in buf.FIELDS)
+    other = _filled(image, 0)
+    other.load_state_dict(sd)
+    assert (other.pos, other.size) == (buf.pos, n)
+    for k in buf.FIELDS:
+        assert other.__dict__[k].dtype == buf.__dict__[k].dtype and torch.equal(other.__dict__[k][:n], buf.__dict__[k][:n]), k
+    g = lambda: torch.Generator().manual_seed(2)   # noqa: E731
+    a, b = buf.sample(16, g()), other.sample(16, g())
+    assert torch.equal(a["rewards"], b["rewards"]) and torch.equal(a["actions"], b["actions"]) and torch.equal(a["dones"], b["dones"])
+    small = _filled(image, 0, capacity=n - 1)
+    with pytest.raises(ValueError, match=f"checkpointed buffer holds {n} transitions, this buffer only {n - 1}"):
+        small.load_state_dict(sd)
+    assert small.size == 0 and small.pos == 0
+
+
 def test_learner_stores_terminal_observations_and_follows_the_sb3_counters():
     torch.manual_seed(0)
     env = CountingEnv(B=6)

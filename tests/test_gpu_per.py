@@ -235,3 +235,32 @@ def test_per_learner_on_the_image_environment_learns_and_resumes_exactly(tmp_pat
     assert torch.equal(flat(a), flat(c))
     assert torch.equal(a.buffer.sum_tree.tree, c.buffer.sum_tree.tree)
     assert torch.equal(a.buffer.img, c.buffer.img)
+
+
+def test_replay_buffer_with_per_kwargs_samples_updates_and_round_trips():
+    """``ReplayBuffer(..., per_kwargs={})`` alone: four adds of four rows into a ring of ten."""
+    dev = torch.device(DEV)
+    buf = dqn_train.ReplayBuffer(10, 46, dev, per_kwargs={})
+    assert dqn_train.ReplayBuffer(10, 46, dev).sum_tree is None and buf.sum_tree.capacity == 10
+    for k in range(4):
+        o = torch.full((4, 46), float(k), device=dev)
+        buf.add(o, o + 0.5, torch.full((4,), k, device=dev), torch.full((4,), -float(k), device=dev), torch.zeros(4, device=dev))
+    assert buf.size == 10 and buf.pos == 6 and per_numpy.check_invariant(buf.sum_tree.tree.cpu().numpy())
+    s = buf.sample(8, torch.Generator(device=dev).manual_seed(1))
+    assert list(s) == ["obs", "actions", "rewards", "next_obs", "dones", "indices", "weights"]
+    # rows that are in the buffer: leaf index - (capacity - 1) is the ring position
+    pos = s["indices"] - 9
+    assert s["indices"].dtype == torch.int64 and int(pos.min()) >= 0 and int(pos.max()) < 10
+    assert torch.equal(s["obs"], buf.obs[pos]) and torch.equal(s["next_obs"], s["obs"] + 0.5)
+    assert torch.equal(s["rewards"], -s["obs"][:, 0]) and torch.equal(s["actions"].float(), s["obs"][:, 0])
+    assert s["weights"].dtype == torch.float32 and s["weights"].shape == (8,)
+    assert float(s["weights"].max()) == 1.0 and float(s["weights"].min()) > 0.0
+    before = buf.sum_tree.tree.clone()
+    buf.update_priorities(s["indices"], torch.linspace(-2.0, 2.0, 8, device=dev))
+    assert not torch.equal(before, buf.sum_tree.tree) and per_numpy.check_invariant(buf.sum_tree.tree.cpu().numpy())
+    sd = buf.state_dict()
+    assert list(sd) == ["pos", "size", "obs", "next_obs", "actions", "rewards", "dones", "per"]
+    other = dqn_train.ReplayBuffer(10, 46, dev, per_kwargs=dict(refresh_tree_freq=7))      # accepted and ignored
+    other.load_state_dict(sd)
+    assert torch.equal(other.sum_tree.tree, buf.sum_tree.tree) and torch.equal(other.sum_tree.state[:4], buf.sum_tree.state[:4])
+    assert (other.pos, other.size) == (6, 10) and torch.equal(other.obs, buf.obs)

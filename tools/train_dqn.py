@@ -129,12 +129,7 @@ def main():
         sys.exit("train_dqn.py: --graph is not built for --images (the image update runs eagerly)")
     if args.fused and (args.images or args.graph):
         sys.exit("train_dqn.py: --fused is built for the ray network and excludes --graph")
-    q_net = dqn_train.ImageQNetwork(env.image_shape) if args.images else None
-    if args.fused:
-        trainer = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.dqn_fused").FusedDqnTrainer(
-            device=f"cuda:{local}", double_q=args.double_q, lr=1e-3)
-    else:
-        trainer = dqn_train.DqnTrainer(q_net=q_net, device=f"cuda:{local}", double_q=args.double_q, lr=1e-3)
+    trainer = dqn_train.make_trainer(env, fused=args.fused, device=f"cuda:{local}", double_q=args.double_q, lr=1e-3)
     buffer_size = args.buffer_size or (200_000 if args.images else 2_000_000)
     learner = dqn_train.DqnLearner(env, trainer, buffer_size=buffer_size, learning_starts=4 * args.envs,
                                    batch_size=args.batch_size, train_freq=4, gradient_steps=args.gradient_steps,

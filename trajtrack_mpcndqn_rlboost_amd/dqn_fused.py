@@ -1,6 +1,7 @@
 """Fused DQN update of the ray Q-network: host side of ``include/mpcgpu_dqn.h``.
 
-:class:`FusedDqnTrainer` has the surface of :class:`dqn_train.DqnTrainer` that :class:`dqn_train.DqnLearner` uses, but its
+:class:`FusedDqnTrainer` is a :class:`dqn_train.DqnTrainerBase` like :class:`dqn_train.DqnTrainer` -- the process group and
+the update / target-sync counters are the base's, the surface :class:`dqn_train.DqnLearner` uses is the same -- but its
 update is ONE launch of ``csrc/dqngpu.hip`` instead of ~40 torch kernels, and :meth:`FusedDqnTrainer.train` runs K updates
 on a uniform replay buffer in one launch.  Parameters, target parameters, Adam moments and the step count live in one state
 block on the device; ``q_net`` and ``q_net_target`` are real ``QNetwork`` modules whose parameters are views into it.
@@ -15,6 +16,7 @@ import torch
 import torch.distributed as dist
 
 from .dqn import N_ACTIONS, OBS_DIM, QNetwork
+from .dqn_train import DqnTrainerBase
 from .solver import MpcGpuError, bind_exports, load_library
 
 N_PARAMS = 1177
@@ -108,7 +110,7 @@ class _AdamView:
         self._tr.load_optimizer_state(sd)
 
 
-class FusedDqnTrainer:
+class FusedDqnTrainer(DqnTrainerBase):
     def __init__(self, q_net: Optional[QNetwork] = None, lr: float = 1e-4, gamma: float = 0.98,
                  target_update_interval: int = 10_000, max_grad_norm: float = 10.0, double_q: bool = False,
                  device: str = "cuda", force_collective: bool = False, seed: int = 0):
@@ -121,10 +123,7 @@ class FusedDqnTrainer:
         self.device_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", self.device_index)
         self._lib = _bind(load_library())
-        self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-        if force_collective and not (dist.is_available() and dist.is_initialized()):
-            raise RuntimeError("force_collective needs an initialised process group")
-        self._collective = self.world > 1 or force_collective
+        super().__init__(target_update_interval, force_collective)
         self.state = torch.zeros(self._lib.mpcgpu_dqn_state_floats(), dtype=torch.float32, device=self.device)
         with torch.no_grad():
             self.state[:N_PARAMS] = torch.cat([p.detach().reshape(-1).float() for p in src.parameters()]).to(self.device)
@@ -138,8 +137,6 @@ class FusedDqnTrainer:
         self._groups = adam_groups(lr)
         self.optimizer = _AdamView(self)
         self.gamma, self.max_grad_norm, self.double_q = gamma, max_grad_norm, bool(double_q)
-        self.target_update_interval = target_update_interval
-        self.num_updates = 0
         self.seed, self.serial = int(seed), 0           # the sample stream of train(): step s draws from (seed, serial + s)
         self._bucket = torch.zeros(N_PARAMS, dtype=torch.float32, device=self.device)     # the gradient, and the all-reduce bucket
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -211,9 +208,7 @@ class FusedDqnTrainer:
             self.apply(self._bucket, 1.0 / self.world)
         else:
             self._call(self._lib.mpcgpu_dqn_step_dev, batch)
-        self.num_updates += 1
-        if self.target_update_interval and self.num_updates % self.target_update_interval == 0:
-            self.sync_target()
+        self._count_updates()
         return self._loss[0]
 
     def train(self, buffer, k: int, batch_size: int) -> torch.Tensor:
@@ -241,7 +236,7 @@ class FusedDqnTrainer:
                 buffer.actions.data_ptr(), buffer.rewards.data_ptr(), buffer.dones.data_ptr(), int(buffer.size), int(batch_size),
                 part, self.seed % 2 ** 64, self.serial % 2 ** 64, losses[done:].data_ptr(), self._stream()))
             self.serial += part
-            self.num_updates += part
+            self._count_updates(part, sync=False)
             done += part
         return losses
 
@@ -249,7 +244,7 @@ class FusedDqnTrainer:
         """Hard target update: a copy of 1 177 floats inside the state block."""
         with torch.no_grad():
             self.state[N_PARAMS:2 * N_PARAMS].copy_(self.state[:N_PARAMS])
-        self.num_target_syncs = getattr(self, "num_target_syncs", 0) + 1
+        self.num_target_syncs += 1
 
     def load_optimizer_state(self, sd: Dict) -> None:
         """Adam's moments and step count from the form of ``torch.optim.Adam.state_dict()``; checked before anything is written."""

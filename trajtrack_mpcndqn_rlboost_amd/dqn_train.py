@@ -21,17 +21,36 @@ from .dqn import ImageQNetwork, QNetwork
 from .per_tree import SumTree
 
 
-class DqnTrainer:
+class DqnTrainerBase:
+    """What :class:`DqnTrainer` and :class:`dqn_fused.FusedDqnTrainer` share: the process group (``world``, ``collective``) and
+    the update / target-sync counters.  The rest of what :class:`DqnLearner` uses -- ``q_net``, ``q_net_target``, ``optimizer``,
+    ``update``, ``last_td_error``, ``sync_target``, ``load_optimizer_state`` -- is each class's own."""
+
+    def __init__(self, target_update_interval: int, force_collective: bool = False):
+        """``force_collective``: all-reduce the gradient (and run what is built around that) in a process group of ONE rank
+        too -- the multi-rank code path, collective included, on a single GPU (tests)."""
+        grouped = dist.is_available() and dist.is_initialized()
+        if force_collective and not grouped:
+            raise RuntimeError("force_collective needs an initialised process group")
+        self.world = dist.get_world_size() if grouped else 1
+        self._collective = self.world > 1 or force_collective
+        self.target_update_interval, self.num_updates, self.num_target_syncs = target_update_interval, 0, 0
+
+    collective = property(lambda self: self._collective, doc="Whether an update all-reduces its gradient (read-only).")
+
+    def _count_updates(self, n: int = 1, sync: bool = True) -> None:
+        """``n`` updates were made: count them and, with ``sync``, apply ``target_update_interval``."""
+        self.num_updates += n
+        if sync and self.target_update_interval and self.num_updates % self.target_update_interval == 0:
+            self.sync_target()
+
+
+class DqnTrainer(DqnTrainerBase):
     def __init__(self, q_net: Optional[QNetwork] = None, lr: float = 1e-4, gamma: float = 0.98,
                  target_update_interval: int = 10_000, max_grad_norm: float = 10.0, double_q: bool = False,
                  device: str = "cpu", force_collective: bool = False):
-        """``force_collective``: run the gradient all-reduce (and the two-graph replay built around it) even when the process
-        group has ONE rank -- the multi-rank code path, collective included, on a single GPU (tests)."""
+        super().__init__(target_update_interval, force_collective)
         self.q_net = (q_net if q_net is not None else QNetwork()).to(device)
-        self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-        if force_collective and not (dist.is_available() and dist.is_initialized()):
-            raise RuntimeError("force_collective needs an initialised process group")
-        self._collective = self.world > 1 or force_collective
         self._params = [p for p in self.q_net.parameters()]
         self._bucket = torch.zeros(sum(p.numel() for p in self._params), dtype=torch.float32, device=device)
         if self.world > 1:
@@ -44,8 +63,6 @@ class DqnTrainer:
         self.q_net_target = copy.deepcopy(self.q_net).requires_grad_(False)
         self.optimizer = torch.optim.Adam(self.q_net.parameters(), lr=lr)
         self.gamma, self.max_grad_norm, self.double_q = gamma, max_grad_norm, double_q
-        self.target_update_interval = target_update_interval
-        self.num_updates = 0
 
     def td_target(self, rewards, next_obs, dones) -> torch.Tensor:
         with torch.no_grad():
@@ -94,9 +111,7 @@ class DqnTrainer:
         """batch (this rank's shard): obs [b,46] f32, actions [b] i64, rewards [b], next_obs [b,46], dones [b]; with
         ``weights`` [b] f32 (prioritized replay) the loss is weighted per row and ``last_td_error`` [b] holds the TD errors."""
         loss = self._eager_step(batch)
-        self.num_updates += 1
-        if self.target_update_interval and self.num_updates % self.target_update_interval == 0:
-            self.sync_target()
+        self._count_updates()
         return loss
 
     # ---- hipGraph path: the update is ~40 tiny kernels (MLP forward / backward, Huber loss, clip, Adam) on 1 177
@@ -119,8 +134,7 @@ class DqnTrainer:
         if weighted:
             self._g_batch["weights"] = torch.ones(batch_size, device=dev)
         self._g_loss = torch.zeros((), device=dev)
-        keep_interval, self.target_update_interval = self.target_update_interval, 0
-        state = ([p.detach().clone() for p in self._params], self.num_updates)
+        before = [p.detach().clone() for p in self._params]     # _eager_step neither counts updates nor syncs the target
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                      # warm-up off the capture (allocations, Adam state)
@@ -140,12 +154,10 @@ class DqnTrainer:
                 self._unpack([p.grad for p in self._params], 1.0 / self.world)
                 self._apply()
         with torch.no_grad():                              # undo the warm-up / capture steps on the zero batch
-            for p, p0 in zip(self._params, state[0]):
+            for p, p0 in zip(self._params, before):
                 p.copy_(p0)
             for st in self.optimizer.state.values():
                 st["exp_avg"].zero_(); st["exp_avg_sq"].zero_(); st["step"].zero_()
-        self.num_updates = state[1]
-        self.target_update_interval = keep_interval
 
     def _backward(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
         target = self.td_target(batch["rewards"], batch["next_obs"], batch["dones"])
@@ -180,9 +192,7 @@ class DqnTrainer:
         if self._collective:
             dist.all_reduce(self._bucket, op=dist.ReduceOp.SUM)
             self._graph_b.replay()
-        self.num_updates += 1
-        if self.target_update_interval and self.num_updates % self.target_update_interval == 0:
-            self.sync_target()
+        self._count_updates()
         return self._g_loss
 
     def load_optimizer_state(self, sd: Dict) -> None:
@@ -226,7 +236,7 @@ class DqnTrainer:
     def sync_target(self) -> None:
         """Hard target update (SB3 ``polyak_update`` with tau = 1)."""
         self.q_net_target.load_state_dict(self.q_net.state_dict())
-        self.num_target_syncs = getattr(self, "num_target_syncs", 0) + 1
+        self.num_target_syncs += 1
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -242,118 +252,67 @@ def flatten_observation(obs: Dict[str, torch.Tensor]) -> torch.Tensor:
 
 
 class ReplayBuffer:
-    """Uniform ring buffer, resident on the environment's device (transitions never visit the host)."""
+    """``ReplayBuffer(capacity, obs_dim, device)``: ring buffer, resident on the environment's device (transitions never visit
+    the host), written against ``FIELDS`` and three hooks for the observation storage (:class:`ImageReplayBuffer`).  Uniform
+    (``sum_tree`` is None) unless ``per_kwargs``, a dictionary, makes it prioritized experience replay: the priorities of the
+    stored transitions are the leaves of a device-resident sum tree (:class:`per_tree.SumTree`, csrc/pergpu.hip).  Keyword names
+    are the reference's (``PerReplayBuffer``, src/pkg_dqn/utils/per_dqn.py:43-56); ``refresh_tree_freq`` is accepted and
+    ignored -- inner nodes here are always the sum of their children and never drift."""
 
-    def __init__(self, capacity: int, obs_dim: int, device):
-        self.capacity, self.device = int(capacity), device
-        self.obs = torch.zeros(self.capacity, obs_dim, dtype=torch.float32, device=device)
+    FIELDS = ("obs", "next_obs", "actions", "rewards", "dones")
+
+    def __init__(self, capacity: int, *shape_and_device, per_kwargs: Optional[Dict] = None):
+        *shape, self.device = shape_and_device
+        self.capacity = int(capacity)
+        self._allocate_obs(*shape)
+        self.actions = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
+        self.rewards = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+        self.dones = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+        self.pos, self.size = 0, 0
+        self.sum_tree = None if per_kwargs is None else SumTree(
+            self.capacity, self.device, **{k: v for k, v in per_kwargs.items() if k != "refresh_tree_freq"})
+
+    def _allocate_obs(self, obs_dim: int) -> None:
+        self.obs = torch.zeros(self.capacity, obs_dim, dtype=torch.float32, device=self.device)
         self.next_obs = torch.zeros_like(self.obs)
-        self.actions = torch.zeros(self.capacity, dtype=torch.int64, device=device)
-        self.rewards = torch.zeros(self.capacity, dtype=torch.float32, device=device)
-        self.dones = torch.zeros(self.capacity, dtype=torch.float32, device=device)
-        self.pos, self.size = 0, 0
 
-    def add(self, obs, next_obs, actions, rewards, dones) -> None:
-        n = obs.shape[0]
-        idx = (self.pos + torch.arange(n, device=self.device)) % self.capacity
+    def _store_obs(self, idx: torch.Tensor, obs, next_obs) -> None:
         self.obs[idx], self.next_obs[idx] = obs, next_obs
-        self.actions[idx] = actions.to(torch.int64)
-        self.rewards[idx] = rewards.to(torch.float32)
-        self.dones[idx] = dones.to(torch.float32)
-        self.pos = (self.pos + n) % self.capacity
-        self.size = min(self.size + n, self.capacity)
 
-    def sample(self, n: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
-        return self._rows(torch.randint(0, self.size, (n,), device=self.device, generator=generator))
-
-    def _rows(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return dict(obs=self.obs[idx], actions=self.actions[idx], rewards=self.rewards[idx],
-                    next_obs=self.next_obs[idx], dones=self.dones[idx])
-
-
-class ImageReplayBuffer:
-    """The same ring buffer for the image observation: images stay uint8 (3 H W bytes each, 8 748 at 54 x 54), the
-    internal observation float32.  One transition holds two observations: 17.6 KB at 54 x 54, so the reference's
-    default of 1e6 transitions takes 17.6 GB of device memory."""
-
-    def __init__(self, capacity: int, image_shape, n_internal: int, device):
-        self.capacity, self.device = int(capacity), device
-        self.img = torch.zeros((self.capacity,) + tuple(image_shape), dtype=torch.uint8, device=device)
-        self.next_img = torch.zeros_like(self.img)
-        self.internal = torch.zeros(self.capacity, n_internal, dtype=torch.float32, device=device)
-        self.next_internal = torch.zeros_like(self.internal)
-        self.actions = torch.zeros(self.capacity, dtype=torch.int64, device=device)
-        self.rewards = torch.zeros(self.capacity, dtype=torch.float32, device=device)
-        self.dones = torch.zeros(self.capacity, dtype=torch.float32, device=device)
-        self.pos, self.size = 0, 0
-
-    FIELDS = ("img", "next_img", "internal", "next_internal", "actions", "rewards", "dones")
-
-    def add(self, obs, next_obs, actions, rewards, dones) -> None:
-        n = obs["internal"].shape[0]
-        idx = (self.pos + torch.arange(n, device=self.device)) % self.capacity
-        self.img[idx], self.next_img[idx] = obs["external"], next_obs["external"]
-        self.internal[idx], self.next_internal[idx] = obs["internal"], next_obs["internal"]
-        self.actions[idx] = actions.to(torch.int64)
-        self.rewards[idx] = rewards.to(torch.float32)
-        self.dones[idx] = dones.to(torch.float32)
-        self.pos = (self.pos + n) % self.capacity
-        self.size = min(self.size + n, self.capacity)
-
-    def sample(self, n: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
-        return self._rows(torch.randint(0, self.size, (n,), device=self.device, generator=generator))
-
-    def _rows(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return dict(obs={"external": self.img[idx], "internal": self.internal[idx]}, actions=self.actions[idx],
-                    rewards=self.rewards[idx], next_obs={"external": self.next_img[idx], "internal": self.next_internal[idx]},
-                    dones=self.dones[idx])
-
-    def state_dict(self) -> Dict:
-        n = self.size
-        return dict(pos=self.pos, size=n, **{k: getattr(self, k)[:n].clone() for k in self.FIELDS})
-
-    def load_state_dict(self, src: Dict) -> None:
-        n = src["size"]
-        if n > self.capacity:
-            raise ValueError(f"checkpointed buffer holds {n} transitions, this buffer only {self.capacity}")
-        for k in self.FIELDS:
-            getattr(self, k)[:n] = src[k].to(self.device)
-        self.pos, self.size = src["pos"] % self.capacity, n
-
-
-class _Prioritized:
-    """Prioritized experience replay on top of a ring buffer: the priorities of the stored transitions are the leaves of a
-    device-resident sum tree (:class:`per_tree.SumTree`, csrc/pergpu.hip).  Keyword names are the reference's
-    (``PerReplayBuffer``, src/pkg_dqn/utils/per_dqn.py:43-56); ``refresh_tree_freq`` is accepted and ignored -- inner nodes
-    here are always the sum of their children and never drift."""
-
-    def _init_tree(self, alpha=0.3, beta=0.4, epsilon=1e-3, update_max_freq=1_000, refresh_tree_freq=50_000,
-                   initial_priority=1):
-        self.sum_tree = SumTree(self.capacity, self.device, alpha=alpha, beta=beta, epsilon=epsilon,
-                                update_max_freq=update_max_freq, initial_priority=initial_priority)
+    def _read_obs(self, idx: torch.Tensor, prefix: str):       # prefix "": the observations of the rows idx; "next_": the next ones
+        return getattr(self, prefix + "obs")[idx]
 
     def add(self, obs, next_obs, actions, rewards, dones) -> None:
         n = actions.shape[0]
-        self.sum_tree.add(self.pos, n, self.size)      # the new rows take the running maximum priority
-        super().add(obs, next_obs, actions, rewards, dones)
+        if self.sum_tree is not None:
+            self.sum_tree.add(self.pos, n, self.size)      # the new rows take the running maximum priority
+        idx = (self.pos + torch.arange(n, device=self.device)) % self.capacity
+        self._store_obs(idx, obs, next_obs)
+        self.actions[idx] = actions.to(torch.int64)
+        self.rewards[idx] = rewards.to(torch.float32)
+        self.dones[idx] = dones.to(torch.float32)
+        self.pos, self.size = (self.pos + n) % self.capacity, min(self.size + n, self.capacity)
 
     def sample(self, n: int, generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
-        """Stratified by priority.  The usual batch plus ``indices`` (tree indices, for :meth:`update_priorities`) and
-        ``weights`` (importance weights, float32, normalised by their maximum)."""
+        """Uniform; with the sum tree stratified by priority, and the batch then also holds ``indices`` (tree indices, for
+        :meth:`update_priorities`) and ``weights`` (importance weights, float32, normalised by their maximum)."""
+        if self.sum_tree is None:
+            return self._rows(torch.randint(0, self.size, (n,), device=self.device, generator=generator))
         u = torch.rand(n, dtype=torch.float64, device=self.device, generator=generator)
         indices, positions, weights = self.sum_tree.sample(u, self.size)
-        batch = self._rows(positions)
-        batch["indices"], batch["weights"] = indices, weights
-        return batch
+        return dict(self._rows(positions), indices=indices, weights=weights)
+
+    def _rows(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
+        return dict(obs=self._read_obs(idx, ""), actions=self.actions[idx], rewards=self.rewards[idx],
+                    next_obs=self._read_obs(idx, "next_"), dones=self.dones[idx])
 
     def update_priorities(self, indices: torch.Tensor, td_error: torch.Tensor) -> None:
         self.sum_tree.update(indices, td_error)
 
     def state_dict(self) -> Dict:
         n = self.size
-        d = dict(pos=self.pos, size=n, **{k: getattr(self, k)[:n].clone() for k in self.FIELDS})
-        d["per"] = self.sum_tree.state_dict(n)
-        return d
+        return dict(pos=self.pos, size=n, **{k: getattr(self, k)[:n].clone() for k in self.FIELDS},
+                    **({} if self.sum_tree is None else dict(per=self.sum_tree.state_dict(n))))
 
     def load_state_dict(self, src: Dict) -> None:
         n = src["size"]
@@ -362,25 +321,36 @@ class _Prioritized:
         for k in self.FIELDS:
             getattr(self, k)[:n] = src[k].to(self.device)
         self.pos, self.size = src["pos"] % self.capacity, n
-        self.sum_tree.load_state_dict(src["per"])
+        if self.sum_tree is not None:
+            self.sum_tree.load_state_dict(src["per"])
 
 
-class PrioritizedReplayBuffer(_Prioritized, ReplayBuffer):
-    FIELDS = ("obs", "next_obs", "actions", "rewards", "dones")
+class ImageReplayBuffer(ReplayBuffer):
+    """The same ring buffer for the image observation, ``ImageReplayBuffer(capacity, image_shape, n_internal, device)``:
+    images stay uint8 (3 H W bytes each, 8 748 at 54 x 54), the internal observation float32.  One transition holds two
+    observations: 17.6 KB at 54 x 54, so the reference's default of 1e6 transitions takes 17.6 GB of device memory."""
 
-    def __init__(self, capacity: int, obs_dim: int, device, **per_kwargs):
-        ReplayBuffer.__init__(self, capacity, obs_dim, device)
-        self._init_tree(**per_kwargs)
+    FIELDS = ("img", "next_img", "internal", "next_internal", "actions", "rewards", "dones")
+
+    def _allocate_obs(self, image_shape, n_internal: int) -> None:
+        self.img = torch.zeros((self.capacity,) + tuple(image_shape), dtype=torch.uint8, device=self.device)
+        self.next_img = torch.zeros_like(self.img)
+        self.internal = torch.zeros(self.capacity, n_internal, dtype=torch.float32, device=self.device)
+        self.next_internal = torch.zeros_like(self.internal)
+
+    def _store_obs(self, idx: torch.Tensor, obs, next_obs) -> None:
+        self.img[idx], self.next_img[idx] = obs["external"], next_obs["external"]
+        self.internal[idx], self.next_internal[idx] = obs["internal"], next_obs["internal"]
+
+    def _read_obs(self, idx: torch.Tensor, prefix: str):
+        return {"external": getattr(self, prefix + "img")[idx], "internal": getattr(self, prefix + "internal")[idx]}
 
 
-class PrioritizedImageReplayBuffer(_Prioritized, ImageReplayBuffer):
-    def __init__(self, capacity: int, image_shape, n_internal: int, device, **per_kwargs):
-        ImageReplayBuffer.__init__(self, capacity, image_shape, n_internal, device)
-        self._init_tree(**per_kwargs)
-
-
-def _clone_obs(obs):
-    return {k: v.clone() for k, v in obs.items()} if isinstance(obs, dict) else obs.clone()
+def _map_obs(fn, obs):
+    """``fn`` of an observation the loop stands at: a tensor (rays), a dictionary of tensors (images) or None (no loop yet)."""
+    if obs is None:
+        return None
+    return {k: fn(v) for k, v in obs.items()} if isinstance(obs, dict) else fn(obs)
 
 
 def exploration_rate(step: int, total: int, fraction: float = 0.2, initial: float = 1.0, final: float = 0.05) -> float:
@@ -389,6 +359,16 @@ def exploration_rate(step: int, total: int, fraction: float = 0.2, initial: floa
     if progress > fraction:
         return final
     return initial + progress * (final - initial) / fraction
+
+
+def make_trainer(env, fused: bool = False, **kw) -> DqnTrainerBase:
+    """The trainer :class:`DqnLearner` defaults to on ``env``: :class:`dqn.ImageQNetwork` on an image environment, the fused
+    HIP update (:class:`dqn_fused.FusedDqnTrainer`) with ``fused``; ``kw`` are the trainer's arguments."""
+    kw.setdefault("device", str(env.device))
+    if fused:
+        from .dqn_fused import FusedDqnTrainer
+        return FusedDqnTrainer(**kw)
+    return DqnTrainer(q_net=ImageQNetwork(env.image_shape) if getattr(env, "is_image_env", False) else None, **kw)
 
 
 class DqnLearner:
@@ -415,8 +395,7 @@ class DqnLearner:
         (DESIGN.md 8.6).  With uniform replay and one rank the whole update round of ``learn`` is ONE launch that draws its
         own minibatches from the counter stream ``(seed + rank, serial)`` -- both are part of ``state_dict`` --; with
         ``per=True`` or several ranks it is one fused update per step around the tree's kernels or the all-reduce."""
-        self.env = env
-        self.device = env.device
+        self.env, self.device = env, env.device
         self.image = bool(getattr(env, "is_image_env", False))
         if self.image and use_graph:
             raise ValueError("use_graph=True is not built for the image environment: its updates run eagerly")
@@ -426,45 +405,34 @@ class DqnLearner:
         if self.fused and use_graph:
             raise ValueError("fused=True and use_graph=True exclude each other: the fused update is one launch already")
         rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        if trainer is None:
+            trainer = make_trainer(env, fused=self.fused)
         if self.fused:
             from .dqn_fused import FusedDqnTrainer
-            if trainer is None:
-                trainer = FusedDqnTrainer(device=str(self.device))
-            elif not isinstance(trainer, FusedDqnTrainer):
+            if not isinstance(trainer, FusedDqnTrainer):
                 raise ValueError("fused=True needs a dqn_fused.FusedDqnTrainer")
             trainer.seed, trainer.serial = seed + rank, 0
-        if trainer is None:
-            q_net = ImageQNetwork(env.image_shape) if self.image else None
-            trainer = DqnTrainer(q_net=q_net, device=str(self.device))
         self.trainer = trainer
         self.trainer.target_update_interval = 0   # the learner syncs on environment steps, as SB3 does
         self.per = bool(per)
-        if self.per and self.image:
-            self.buffer = PrioritizedImageReplayBuffer(buffer_size, env.image_shape, 14, self.device, **(per_kwargs or {}))
-        elif self.per:
-            self.buffer = PrioritizedReplayBuffer(buffer_size, 46, self.device, **(per_kwargs or {}))
-        elif self.image:
-            self.buffer = ImageReplayBuffer(buffer_size, env.image_shape, 14, self.device)
-        else:
-            self.buffer = ReplayBuffer(buffer_size, 46, self.device)
+        self.buffer = (ImageReplayBuffer if self.image else ReplayBuffer)(
+            buffer_size, *((env.image_shape, 14) if self.image else (46,)), self.device,
+            per_kwargs=(per_kwargs or {}) if self.per else None)
         self.learning_starts, self.batch_size, self.train_freq = learning_starts, batch_size, train_freq
         self.gradient_steps, self.target_update_interval = gradient_steps, target_update_interval
         self.eps = (exploration_fraction, exploration_initial_eps, exploration_final_eps)
         self.gen = torch.Generator(device=self.device)
-        self.gen.manual_seed(seed + (dist.get_rank() if dist.is_available() and dist.is_initialized() else 0))
+        self.gen.manual_seed(seed + rank)
         self.num_timesteps, self.n_calls = 0, 0
         self.episode_returns, self.episode_successes = [], []
         # track_episodes=False keeps the episode statistics as device counters (no host synchronisation in the loop)
         self.track_episodes = track_episodes
-        self.ep_count = torch.zeros((), dtype=torch.float64, device=self.device)
-        self.ep_return_sum = torch.zeros((), dtype=torch.float64, device=self.device)
-        self.ep_success_sum = torch.zeros((), dtype=torch.float64, device=self.device)
-        self.use_graph = use_graph
+        self.ep_count, self.ep_return_sum, self.ep_success_sum = (torch.zeros((), dtype=torch.float64, device=self.device) for _ in range(3))
         if use_graph:
-            if self.per:
-                self.trainer.enable_graph(batch_size, weighted=True)
-            else:
-                self.trainer.enable_graph(batch_size)
+            self.trainer.enable_graph(batch_size, weighted=self.per)
+        # decided once: one step's update, and whether a round is ONE launch that samples the buffer itself (fused, uniform, one rank)
+        self._update = self.trainer.update_graphed if use_graph else self.trainer.update
+        self._one_launch = self.fused and not self.per and not self.trainer.collective
         # state of the collection loop between two learn() calls (a run can be checkpointed and resumed in the middle)
         self._obs, self._ep_return, self.n_updates = None, None, 0
         self._last_loss = torch.zeros((), device=self.device)
@@ -486,21 +454,16 @@ class DqnLearner:
     def state_dict(self, include_buffer: bool = True) -> Dict:
         tr = self.trainer
         d = dict(q_net=tr.q_net.state_dict(), q_net_target=tr.q_net_target.state_dict(), optimizer=tr.optimizer.state_dict(),
-                 num_updates=tr.num_updates, num_target_syncs=getattr(tr, "num_target_syncs", 0),
+                 num_updates=tr.num_updates, num_target_syncs=tr.num_target_syncs,
                  num_timesteps=self.num_timesteps, n_calls=self.n_calls, n_updates=self.n_updates,
                  generator=self.gen.get_state(), episode_returns=list(self.episode_returns),
                  episode_successes=list(self.episode_successes), ep_count=self.ep_count.clone(),
                  ep_return_sum=self.ep_return_sum.clone(), ep_success_sum=self.ep_success_sum.clone(),
-                 obs=None if self._obs is None else _clone_obs(self._obs),
-                 ep_return=None if self._ep_return is None else self._ep_return.clone())
+                 obs=_map_obs(torch.clone, self._obs), ep_return=_map_obs(torch.clone, self._ep_return))
         if self.fused:
             d["fused_seed"], d["fused_serial"] = tr.seed, tr.serial
-        if include_buffer and (self.image or self.per):
+        if include_buffer:
             d["buffer"] = self.buffer.state_dict()
-        elif include_buffer:
-            b, n = self.buffer, self.buffer.size
-            d["buffer"] = dict(pos=b.pos, size=n, obs=b.obs[:n].clone(), next_obs=b.next_obs[:n].clone(),
-                               actions=b.actions[:n].clone(), rewards=b.rewards[:n].clone(), dones=b.dones[:n].clone())
         if hasattr(self.env, "state_dict"):
             d["env"] = self.env.state_dict()
         return d
@@ -516,23 +479,9 @@ class DqnLearner:
         self.gen.set_state(d["generator"].cpu())   # a generator state is a host ByteTensor, also for a device generator
         self.episode_returns, self.episode_successes = list(d["episode_returns"]), list(d["episode_successes"])
         self.ep_count.copy_(d["ep_count"]); self.ep_return_sum.copy_(d["ep_return_sum"]); self.ep_success_sum.copy_(d["ep_success_sum"])
-        if d["obs"] is None:
-            self._obs = None
-        elif self.image:
-            self._obs = {k: v.to(self.device) for k, v in d["obs"].items()}
-        else:
-            self._obs = d["obs"].to(self.device)
-        self._ep_return = None if d["ep_return"] is None else d["ep_return"].to(self.device)
-        if "buffer" in d and (self.image or self.per):
+        self._obs, self._ep_return = (_map_obs(lambda v: v.to(self.device), d[k]) for k in ("obs", "ep_return"))
+        if "buffer" in d:
             self.buffer.load_state_dict(d["buffer"])
-        elif "buffer" in d:
-            b, src = self.buffer, d["buffer"]
-            n = src["size"]
-            if n > b.capacity:
-                raise ValueError(f"checkpointed buffer holds {n} transitions, this buffer only {b.capacity}")
-            b.obs[:n], b.next_obs[:n] = src["obs"].to(self.device), src["next_obs"].to(self.device)
-            b.actions[:n], b.rewards[:n], b.dones[:n] = (src[k].to(self.device) for k in ("actions", "rewards", "dones"))
-            b.pos, b.size = src["pos"] % b.capacity, n
         if "env" in d and hasattr(self.env, "load_state_dict"):
             self.env.load_state_dict(d["env"])
 
@@ -555,9 +504,7 @@ class DqnLearner:
         if self._obs is None:
             self._obs = self._prepare(env.reset())
             self._ep_return = torch.zeros(B, dtype=torch.float64, device=self.device)
-        obs, ep_return = self._obs, self._ep_return
-        last_loss = self._last_loss
-        n_updates = self.n_updates
+        obs, ep_return, n_updates, last_loss = self._obs, self._ep_return, self.n_updates, self._last_loss
         end = total_timesteps if stop_at is None else min(stop_at, total_timesteps)
         while self.num_timesteps < end:
             collected = 0
@@ -591,28 +538,23 @@ class DqnLearner:
                     break
             if self.num_timesteps > self.learning_starts and self.buffer.size >= self.batch_size:
                 steps = self.gradient_steps if self.gradient_steps >= 0 else collected
-                # fused, uniform replay, one rank: the whole round is one launch that samples the buffer itself
-                one_launch = self.fused and not self.per and not self.trainer._collective
-                if one_launch and steps > 0:
+                if self._one_launch and steps > 0:
                     last_loss = self.trainer.train(self.buffer, steps, self.batch_size)[-1]
-                for _ in range(0 if one_launch else steps):
-                    step = self.trainer.update_graphed if self.use_graph else self.trainer.update
+                for _ in range(0 if self._one_launch else steps):
                     batch = self.buffer.sample(self.batch_size, self.gen)
-                    last_loss = step(batch)
+                    last_loss = self._update(batch)       # eager, a replayed graph or the fused kernel: bound in __init__
                     if self.per:      # the PER kernels run eagerly on the same stream, around the (possibly replayed) update
                         self.buffer.update_priorities(batch["indices"], self.trainer.last_td_error)
                 n_updates += steps
             self._obs, self._ep_return, self.n_updates, self._last_loss = obs, ep_return, n_updates, last_loss
             if callback is not None:
                 callback(self)
-        self._obs, self._ep_return, self.n_updates, self._last_loss = obs, ep_return, n_updates, last_loss
         if not self.track_episodes:       # whole-run averages from the device counters
             n = float(self.ep_count)
             return dict(timesteps=self.num_timesteps, updates=n_updates, loss=float(last_loss), episodes=int(n),
                         mean_return=float(self.ep_return_sum) / n if n else float("nan"),
                         success_rate=float(self.ep_success_sum) / n if n else float("nan"))
         recent = self.episode_returns[-100:]
-        return dict(timesteps=self.num_timesteps, updates=n_updates, loss=float(last_loss),
-                    episodes=len(self.episode_returns),
+        return dict(timesteps=self.num_timesteps, updates=n_updates, loss=float(last_loss), episodes=len(self.episode_returns),
                     mean_return=float(sum(recent) / len(recent)) if recent else float("nan"),
                     success_rate=float(sum(self.episode_successes[-100:]) / max(1, len(self.episode_successes[-100:]))))
