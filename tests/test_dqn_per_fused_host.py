@@ -1,0 +1,211 @@
+"""The prioritized K-step launch without a GPU: the binding table of ``dqn_per_fused`` and its header, the
+uniform draw against Python integers and fractions, the composed numpy twin (tests/support/dqn_per_numpy.py) -- tree invariant,
+strata in exact rational arithmetic, K = K1 + K2 -- and the refusals of ``DqnLearner(per_in_kernel=True)`` and the training tool."""
+import ctypes as C
+import importlib
+import os
+import re
+import sys
+import types
+from fractions import Fraction
+
+import numpy as np
+import pytest
+import torch
+
+from support import dqn_cases, dqn_numpy as tw, dqn_per_numpy as twp, per_numpy
+from trajtrack_mpcndqn_rlboost_amd import dqn_fused, dqn_per_fused, dqn_train, per_tree
+
+solver_mod = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.solver")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+ARGUMENTS = {"mpcgpu_dqn_train_per_dev": 19, "mpcgpu_dqn_per_last_error": 0}
+
+
+def declared(header):
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+    return set(re.findall(r"\b(mpcgpu_[a-z_0-9]+)\s*\(", text))
+
+
+# ---- binding ---------------------------------------------------------------------------------------------------------------
+def test_export_tuple_is_the_key_tuple_of_the_table():
+    assert isinstance(dqn_per_fused.DQN_PER_EXPORTS, tuple) and dqn_per_fused.DQN_PER_EXPORTS == tuple(dqn_per_fused._DQN_PER_TABLE)
+    assert set(dqn_per_fused.DQN_PER_EXPORTS) == set(ARGUMENTS)
+    for name, (restype, argtypes) in dqn_per_fused._DQN_PER_TABLE.items():
+        assert len(argtypes) == ARGUMENTS[name], name
+        assert restype is (C.c_char_p if name.endswith("_last_error") else C.c_int32), name
+    assert not set(dqn_per_fused.DQN_PER_EXPORTS) & (set(dqn_fused.DQN_EXPORTS) | set(per_tree.PER_EXPORTS))
+
+
+def test_a_library_that_lacks_an_export_is_refused_by_name():
+    exports = dqn_per_fused.DQN_PER_EXPORTS
+    for gone in exports:
+        stand_in = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in exports if e != gone})
+        with pytest.raises(solver_mod.MpcGpuError) as err:
+            dqn_per_fused._bind(stand_in)
+        text = str(err.value)
+        assert gone in text and "csrc/dqngpu.hip" in text and "rebuild" in text and "no fallback" in text
+        assert not any(hasattr(fn, "argtypes") for fn in vars(stand_in).values())      # refused before anything was set
+    whole = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in exports})
+    assert dqn_per_fused._bind(whole) is whole and len(whole.mpcgpu_dqn_train_per_dev.argtypes) == 19
+    # the tag is this table's own: a handle bound for the other two tables is still asked for these exports
+    other = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in dqn_fused.DQN_EXPORTS + per_tree.PER_EXPORTS})
+    dqn_fused._bind(other); per_tree._bind(other)
+    with pytest.raises(solver_mod.MpcGpuError, match="mpcgpu_dqn_train_per_dev"):
+        dqn_per_fused._bind(other)
+
+
+def test_the_built_library_and_the_header_have_exactly_these_exports():
+    path = solver_mod.library_path()
+    assert os.path.exists(path), f"{path} missing -- run __graft_entry__.build()"
+    lib = C.CDLL(path)
+    for sym in dqn_per_fused.DQN_PER_EXPORTS:
+        assert hasattr(lib, sym), sym
+    lib.mpcgpu_abi_version.restype = C.c_int32
+    assert lib.mpcgpu_abi_version() == 8
+    assert declared("mpcgpu_dqn_per.h") == set(dqn_per_fused.DQN_PER_EXPORTS)
+    assert not declared("mpcgpu_dqn.h") & set(dqn_per_fused.DQN_PER_EXPORTS)
+    assert not declared("mpcgpu_per.h") & set(dqn_per_fused.DQN_PER_EXPORTS)
+    bound = dqn_per_fused._bind(solver_mod.load_library())
+    assert len(bound.mpcgpu_dqn_train_per_dev.argtypes) == 19 and bound.mpcgpu_dqn_per_last_error.restype is C.c_char_p
+
+
+def test_refusals_of_the_entry_need_no_device():
+    """Every refusal comes before the device is touched, and its text is this entry's own."""
+    lib = dqn_per_fused._bind(dqn_fused._bind(solver_mod.load_library()))
+    dqn = dqn_fused._CDqnParams(1e-4, 0.98, 10.0, 0.9, 0.999, 1e-8, 0, 0)
+    per = per_tree._CPerParams(100, 1000, 0.3, 0.4, 1e-3, 1.0)
+    p = 4096                                                       # any non-null address: a refused call reads none of them
+
+    def call(dqn=dqn, per=per, tree=p, n_entries=50, n=32, K=1):
+        return lib.mpcgpu_dqn_train_per_dev(0, C.byref(dqn), C.byref(per), p, tree, p, p, p, p, p, n_entries, n, K, 1, 0, p, None, None, None)
+    cases = ((dict(n=0), "1 <= n <= 256"), (dict(n=257), "1 <= n <= 256"), (dict(K=0), "1 <= K <= 65536"), (dict(K=65537), "1 <= K <= 65536"),
+             (dict(n_entries=0), "1 <= n_entries <= capacity"), (dict(n_entries=101), "1 <= n_entries <= capacity"),
+             (dict(tree=None), "null pointer"), (dict(dqn=dqn_fused._CDqnParams(0.0, 0.98, 10.0, 0.9, 0.999, 1e-8, 0, 0)), "mpcgpu_dqn_params"),
+             (dict(per=per_tree._CPerParams(0, 1000, 0.3, 0.4, 1e-3, 1.0)), "mpcgpu_per_params"))
+    for kw, text in cases:
+        assert call(**kw) < 0 and text in lib.mpcgpu_dqn_per_last_error().decode(), kw
+
+
+# ---- the uniform draw --------------------------------------------------------------------------------------------------------
+def test_uniform_draw_is_exact_integer_arithmetic():
+    for bits in (0, 1, 2 ** 11 - 1, 2 ** 11, 2 ** 11 + 1, 2 ** 63, 2 ** 64 - 2 ** 11 - 1, 2 ** 64 - 2 ** 11, 2 ** 64 - 1, 0x9E3779B97F4A7C15):
+        u = twp.uniform_of(bits)
+        assert Fraction(u) == Fraction(bits >> 11, 2 ** 53) and 0.0 <= u < 1.0
+        assert (u == 0.0) == (bits < 2 ** 11)
+    assert twp.uniform_of(2 ** 64 - 1) == 1.0 - 2.0 ** -53 != 1.0
+    for seed, serial in ((0, 0), (12345, 7), (2 ** 64 - 1, 2 ** 40 + 3)):
+        bits = twp.draw_bits(seed, serial, 256)
+        # the stream of mpcgpu_dqn_train_dev: the same bits give that entry's rows
+        assert [(b * 1000) >> 64 for b in bits] == tw.sample_rows(seed, serial, 256, 1000).tolist()
+        u = twp.uniforms(seed, serial, 256)
+        assert u.dtype == np.float64 and [Fraction(x) for x in u.tolist()] == [Fraction(b >> 11, 2 ** 53) for b in bits]
+        assert u.max() < 1.0 and len(set(u.tolist())) == 256
+
+
+# ---- the composed twin ---------------------------------------------------------------------------------------------------------
+def filled(rng, capacity, n_entries, rounds=3):
+    """Buffer arrays of ``capacity`` rows and a tree with ``n_entries`` leaves whose priorities differ."""
+    buf = dqn_cases.random_batch(rng, capacity)
+    tree = per_numpy.SumTree(capacity)
+    tree.add(0, n_entries, 0)
+    for _ in range(rounds):
+        idx, _, _ = tree.sample(rng.random(8), n_entries)
+        tree.update(idx, (3.0 * rng.standard_normal(8)).astype(F))
+    return buf, tree
+
+
+def in_order_leaves(C):
+    """Tree indices of the leaves from left to right (the order the descent's cumulative sums run in)."""
+    out, stack = [], [0]
+    while stack:
+        i = stack.pop()
+        if 2 * i + 1 >= 2 * C - 1:
+            out.append(i)
+        else:
+            stack += [2 * i + 2, 2 * i + 1]
+    return out
+
+
+@pytest.mark.parametrize("C_, n_entries, n", [(6, 6, 2), (6, 4, 5), (6, 6, 33)])
+def test_every_row_lands_in_its_stratum_and_the_tree_stays_a_sum_tree(C_, n_entries, n):
+    rng = np.random.default_rng(100 * C_ + n)
+    buf, tree = filled(rng, C_, n_entries)
+    order = in_order_leaves(C_)
+    assert sorted(order) == list(range(C_ - 1, 2 * C_ - 1))
+    seen = []
+
+    def after_step(s, idx, pos, before):
+        assert per_numpy.check_invariant(tree.tree)
+        assert np.array_equal(pos, idx - (C_ - 1)) and pos.min() >= 0 and pos.max() < C_
+        # exact cumulative sums of the leaves as the step found them; the descent works on ROUNDED sums (each inner node one
+        # rounded addition, depth <= 3 here, plus the roundings of a, b, s and one subtraction per level), so a row may miss
+        # its exact stratum by a few ulps of the total: the slack is 16 * 2^-52 * total, nothing measured
+        leaves = [Fraction(float(before[i])) for i in order]
+        total = sum(leaves)
+        slack = total * Fraction(16, 2 ** 52)
+        cum = [sum(leaves[:j], Fraction(0)) for j in range(C_ + 1)]
+        for i in range(n):
+            j = order.index(int(idx[i]))
+            assert before[idx[i]] > 0.0                                        # never a row that holds no transition
+            lo, hi = total * i / n, total * (i + 1) / n
+            assert cum[j + 1] >= lo - slack and cum[j] <= hi + slack, (s, i, j)
+        seen.append(idx.copy())
+    twin = tw.Twin(dqn_cases.random_theta(rng), dqn_cases.random_theta(rng))
+    losses, indices, delta = twp.train_per(twin, tree, buf, n_entries, n, 3, 5, 11, after_step)
+    assert len(seen) == 3 and np.array_equal(indices, np.stack(seen)) and np.isfinite(losses).all() and twin.t == 3
+    if n > n_entries:
+        assert any(len(set(row.tolist())) < n for row in indices)              # repeated indices: the highest row won
+        last = {int(i): r for r, i in enumerate(indices[-1])}
+        want = tree.priorities(delta[-1])
+        for i, r in last.items():
+            assert tree.tree[i] == want[r]
+
+
+def test_k_steps_equal_k1_then_k2_steps():
+    rng = np.random.default_rng(9)
+    theta, target = dqn_cases.random_theta(rng), dqn_cases.random_theta(rng)
+    buf, tree = filled(rng, 37, 30)
+    start = tree.tree.copy()
+    whole, tw_whole = tw.Twin(theta, target), tree
+    a = twp.train_per(whole, tw_whole, buf, 30, 8, 5, 3, 100)
+    parts, tree2 = tw.Twin(theta, target), per_numpy.SumTree(37)
+    tree2.tree[:] = start
+    b1 = twp.train_per(parts, tree2, buf, 30, 8, 2, 3, 100)
+    b2 = twp.train_per(parts, tree2, buf, 30, 8, 3, 3, 102)
+    for x, y1, y2 in zip(a, b1, b2):
+        assert np.array_equal(x, np.concatenate([y1, y2]))
+    assert np.array_equal(whole.theta, parts.theta) and np.array_equal(whole.m, parts.m) and whole.t == parts.t == 5
+    assert np.array_equal(tw_whole.tree, tree2.tree) and not np.array_equal(start, tree2.tree)
+
+
+# ---- learner and tool refusals -------------------------------------------------------------------------------------------------
+def _env():
+    return types.SimpleNamespace(B=4, device=torch.device("cpu"), is_image_env=False, image_shape=(3, 54, 54))
+
+
+def test_per_in_kernel_needs_fused():
+    with pytest.raises(ValueError, match="per_in_kernel=True needs fused=True and per=True"):
+        dqn_train.DqnLearner(_env(), per=True, per_in_kernel=True, buffer_size=8)
+
+
+def test_per_in_kernel_needs_per():
+    with pytest.raises(ValueError, match="per_in_kernel=True needs fused=True and per=True"):
+        dqn_train.DqnLearner(_env(), fused=True, per_in_kernel=True, buffer_size=8)
+
+
+def test_per_in_kernel_is_off_by_default():
+    learner = dqn_train.DqnLearner(_env(), buffer_size=8)
+    assert learner.per_in_kernel is False and learner._one_launch is False
+
+
+def test_training_tool_refuses_per_in_kernel_without_fused_and_per(capsys):
+    sys.path.insert(0, ROOT)
+    train_dqn = importlib.import_module("tools.train_dqn")
+    for argv in (["--per-in-kernel"], ["--per-in-kernel", "--fused"], ["--per-in-kernel", "--per"], ["--per-in-kernel", "--fused", "--per", "--gpus", "2"]):
+        with pytest.raises(SystemExit) as err:
+            train_dqn.parse_args(argv)
+        assert err.value.code == 2 and "--per-in-kernel" in capsys.readouterr().err
+    args = train_dqn.parse_args(["--per-in-kernel", "--fused", "--per"])
+    assert args.per_in_kernel and args.fused and args.per
+    assert not train_dqn.parse_args([]).per_in_kernel

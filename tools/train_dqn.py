@@ -3,14 +3,15 @@
 
     python tools/train_dqn.py [--gpus N] [--envs 4096] [--timesteps 4000000] [--gradient-steps 16] [--batch-size 256]
                               [--save DIR] [--resume DIR/checkpoint.pt] [--checkpoint-every STEPS]
-                              [--images] [--fresh-maps] [--per] [--buffer-size N] [--graph | --fused]
+                              [--images] [--fresh-maps] [--per] [--buffer-size N] [--graph | --fused [--per-in-kernel]]
 
 `--images` trains dqn.ImageQNetwork on the image environment (rl_env.BatchedImgsEnv); with `--fresh-maps` every episode of it
 starts on a new random map too (map_turnover=True, capacity map_stream.DYNAMIC_CAPACITY, stream seed + rank).
 
 `--fused` runs the update as the fused HIP kernel (dqn_fused.FusedDqnTrainer; ray network, batch size at most
 256): with uniform replay and one rank a whole update round is one launch, which makes `--gradient-steps -1` -- one gradient
-step per collected transition, the reference's setting -- affordable.
+step per collected transition, the reference's setting -- affordable.  With `--per` the round is one launch per step around the
+tree's kernels unless `--per-in-kernel` moves sample, update and re-prioritisation into the launch as well.
 
 `--save DIR` writes what the reference's run leaves behind (src/test_block_rl.py:73-76,89-96: EvalCallback's best_model and
 model.save's final_model) -- best_model.pt whenever the mean return of a progress window improves, final_model.pt at the end --
@@ -82,7 +83,7 @@ def self_launch(gpus: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--envs", type=int, default=4096)
@@ -94,6 +95,8 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the update from captured HIP graphs (multi-rank: two graphs around the all-reduce)")
     ap.add_argument("--fused", action="store_true",
                     help="the update as one fused HIP kernel (ray network only); with it --gradient-steps -1 is the reference's ratio")
+    ap.add_argument("--per-in-kernel", action="store_true",
+                    help="with --fused --per on one GPU: sample, update and re-prioritise inside the launch, one launch per update round")
     ap.add_argument("--save", default=None, help="directory for best_model.pt / final_model.pt / checkpoint.pt")
     ap.add_argument("--resume", default=None, help="checkpoint.pt of an earlier run with the same arguments")
     ap.add_argument("--checkpoint-every", type=int, default=0, help="environment steps between checkpoints (0: only at the end)")
@@ -104,7 +107,16 @@ def main():
                     help="train dqn.ImageQNetwork on the image environment (BatchedImgsEnv); combines with --fresh-maps and --per")
     ap.add_argument("--buffer-size", type=int, default=None,
                     help="replay transitions (default 2000000; 200000 with --images, whose transitions hold two uint8 images)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.per_in_kernel and not (args.fused and args.per):
+        ap.error("--per-in-kernel is the prioritized form of the fused K-step launch: it needs --fused and --per")
+    if args.per_in_kernel and args.gpus > 1:
+        ap.error("--per-in-kernel is the one-GPU path: several ranks update step by step around the all-reduce")
+    return args
+
+
+def main():
+    args = parse_args()
     if os.environ.get("WORLD_SIZE") is None and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
@@ -134,7 +146,7 @@ def main():
     learner = dqn_train.DqnLearner(env, trainer, buffer_size=buffer_size, learning_starts=4 * args.envs,
                                    batch_size=args.batch_size, train_freq=4, gradient_steps=args.gradient_steps,
                                    target_update_interval=200_000, exploration_fraction=0.3, use_graph=args.graph,
-                                   track_episodes=False, per=args.per, fused=args.fused)
+                                   track_episodes=False, per=args.per, fused=args.fused, per_in_kernel=args.per_in_kernel)
     ck_name = "checkpoint.pt" if rank == 0 else f"checkpoint.rank{rank}.pt"
     if args.resume:
         learner.load(args.resume if rank == 0 else os.path.join(os.path.dirname(args.resume), ck_name))
@@ -180,6 +192,7 @@ def main():
                           "rccl_ranks": dist.get_world_size() if world > 1 else 1, "backend": "nccl" if world > 1 else None,
                           "updates_per_s": stats["updates"] / dt, "gradient_all_reduce_floats": 1177 if world > 1 else 0,
                           "update_path": ("fused HIP kernels around one flat RCCL all-reduce" if world > 1 else
+                                          "fused HIP kernel with the sum tree inside, one launch per update round" if args.per_in_kernel else
                                           "fused HIP kernel, one launch per step" if args.per else
                                           "fused HIP kernel, one launch per update round") if args.fused else "two HIP graphs around one flat RCCL all-reduce" if (args.graph and world > 1) else
                                          ("one HIP graph" if args.graph else "eager"),

@@ -14,6 +14,15 @@
 // In the K-step loop m, v and theta of the owned slots stay in registers and the state block is written once, at the end.
 // LDS: 256 records of 484 bytes + two padded parameter vectors + the fold's slots = 134 KB of the CU's 160 KB.
 //
+// The kernel is a template over PER.  <false> is the kernel of the four entries as it always was (same registers, scratch and
+// LDS: `make resources`).  <true> (include/mpcgpu_dqn_per.h) adds two phases around A/B/C in every step:
+//   phase S  thread i = row i: u from the counter stream, the descent of the sum tree, the weight; the maximum weight over the rows
+//            and "the highest row of a repeated leaf wins" are settled in 4 KB of LDS (256 doubles, 256 indices);
+//   phase U  the winners store their leaves' new priorities, then every row recomputes its ancestors depth by depth.
+// Descent, weight, priority and the recomputation of an ancestor are per_tree.hpp's, the functions pergpu.hip's kernels call.  The
+// tree stays in global memory and only this workgroup touches it during the launch: a barrier stands between the leaf stores,
+// each depth of the climb and the next step's descent.
+//
 // SUMMATION ORDERS (restated from the header; tests/support/dqn_numpy.py follows them operation by operation): dot products
 // bias first, then k ascending; dh1 from 0, j ascending; gradients from 0, rows ascending; loss and sum of squares over 256
 // slots folded in halves 128, 64, .., 1 (the sum of squares after each lane added its slots in ascending order from 0).
@@ -26,9 +35,11 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "../../include/mpcgpu_dqn.h"
-#include "per_pow.hpp"
+#include "../../include/mpcgpu_dqn_per.h"
+#include "per_tree.hpp"
 
 namespace dqngpu {
 
@@ -79,10 +90,7 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {   // SplitMix64 finalise
     return z ^ (z >> 31);
 }
 
-__device__ inline double pow_as_libm(double x, double y) {
-    double v;
-    return pergpu::libm_pow(x, y, &v) ? v : pow(x, y);
-}
+using pergpu::pow_as_libm;
 
 // out[j] = b[j] + sum over k ascending of W[j][k] * x[k]; W's rows are STRIDE words apart and 16-byte aligned
 template <int IN, int STRIDE, int OUT, bool RELU>
@@ -145,12 +153,26 @@ __device__ __forceinline__ void entry_offsets(int p, int* cofs, int* iofs) {
     else if (p < NP) *cofs = R_DZ2 + (p - OFF_B2);
 }
 
-__global__ void __launch_bounds__(NT) dqn_kernel(const Args a) {
+// the sum tree of a prioritized launch; unused by the four entries of mpcgpu_dqn.h
+struct PerArgs {
+    double* tree;                // [2 C - 1]
+    int64_t* indices;            // [steps][n], may be null
+    int64_t C, n_entries;
+    double alpha, beta, epsilon;
+};
+struct NoTree {};
+
+// The body of every entry.  PER = false: the four entries of mpcgpu_dqn.h, no tree.  PER = true: gradient and apply in every
+// step, the step's rows drawn from the sum tree in front of phase A (phase S) and their leaves re-prioritised behind phase C
+// (phase U), by the functions of per_tree.hpp that the tree's own kernels call.  All tree traffic is this workgroup's; a barrier
+// stands between the leaf stores, each depth of the climb and the next step's descent.
+template <bool PER>
+__global__ void __launch_bounds__(NT) dqn_kernel(const Args a, const std::conditional_t<PER, PerArgs, NoTree> tr) {
     __shared__ __align__(16) float th[L_WORDS], tt[L_WORDS];      // online and target parameters, padded layout
     __shared__ float rec[NT * RS];
     __shared__ float red[NT];
     const int t = threadIdx.x, n = a.n;
-    const bool do_grad = a.mode & DO_GRAD, do_apply = a.mode & DO_APPLY, sample = a.mode & DO_SAMPLE;
+    const bool do_grad = PER || (a.mode & DO_GRAD), do_apply = PER || (a.mode & DO_APPLY), sample = !PER && (a.mode & DO_SAMPLE);
     const float nf = (float)n;
 
     float theta[SLOTS], m[SLOTS], v[SLOTS], g[SLOTS];
@@ -180,11 +202,45 @@ __global__ void __launch_bounds__(NT) dqn_kernel(const Args a) {
     __syncthreads();
 
     for (int s = 0; s < a.steps; ++s) {
+        int64_t leaf = 0;            // PER: this row's tree index, its weight, its delta and whether it is the highest row of its leaf
+        float drawn_w = 1.0f, delta = 0.0f;
+        bool wins = false;
+        if constexpr (PER) {
+            // ---- phase S: the stratified sample of per_sample_kernel, u from the counter stream
+            __shared__ double wred[NT];
+            __shared__ int64_t drawn[NT];
+            const double total = tr.tree[0];
+            double w = -INFINITY;
+            if (t < n) {
+                const uint64_t key = mix64(a.seed + GOLDEN * (a.serial0 + (uint64_t)s));
+                const double u = (double)(mix64(key + GOLDEN * (uint64_t)(t + 1)) >> 11) * 0x1.0p-53;
+                leaf = pergpu::descend(tr.tree, 2 * tr.C - 1, pergpu::stratum_point(total, n, t, u));
+                w = pergpu::raw_weight(tr.n_entries, tr.tree[leaf], total, tr.beta);
+                if (tr.indices) tr.indices[(int64_t)s * n + t] = leaf;
+            }
+            wred[t] = w;
+            drawn[t] = leaf;
+            __syncthreads();
+#pragma unroll
+            for (int h = NT / 2; h > 0; h >>= 1) {
+                if (t < h) wred[t] = wred[t + h] > wred[t] ? wred[t + h] : wred[t];
+                __syncthreads();
+            }
+            drawn_w = (float)(w / wred[0]);
+            // on a repeated index the highest row wins.  Every lane reads every row (a broadcast, and no exit that depends on
+            // what was read, so the reads run back to back): a scan from the row's own index that stops at the first repeat was
+            // a chain of up to 255 LDS latencies and cost 9 us of the 79 us step at 256 rows
+            bool repeated = false;
+#pragma unroll 8
+            for (int j = 0; j < n; ++j) repeated |= (j > t) & (drawn[j] == leaf);
+            wins = t < n && !repeated;
+        }
         if (do_grad) {
             // ---- phase A: one row per thread
             float mine = 0.0f;
             if (t < n) {
                 int64_t row = t;
+                if constexpr (PER) row = leaf - (tr.C - 1);
                 if (sample) {
                     const uint64_t key = mix64(a.seed + GOLDEN * (a.serial0 + (uint64_t)s));
                     row = (int64_t)__umul64hi(mix64(key + GOLDEN * (uint64_t)(t + 1)), (uint64_t)a.size);
@@ -215,8 +271,8 @@ __global__ void __launch_bounds__(NT) dqn_kernel(const Args a) {
                 const float d = y - qa, e = fabsf(d);
                 float l = e < 1.0f ? (0.5f * e) * e : e - 0.5f;
                 float c = e < 1.0f ? -d : (d > 0.0f ? -1.0f : 1.0f);
-                if (a.weights) {
-                    const float w = a.weights[row];
+                if (PER || a.weights) {
+                    const float w = PER ? drawn_w : a.weights[row];
                     l = w * l;
                     c = w * c;
                 }
@@ -258,7 +314,8 @@ __global__ void __launch_bounds__(NT) dqn_kernel(const Args a) {
 #pragma unroll
                 for (int k = 0; k < ACT; ++k) r[R_DZ2 + k] = act == k ? gq : 0.0f;
                 r[R_ONE] = 1.0f;
-                if (a.td) a.td[t] = d;
+                if (a.td) a.td[PER ? (int64_t)s * n + t : t] = d;
+                if constexpr (PER) delta = d;
                 mine = l;
             }
             const float total = fold(red, mine);      // its first barrier also publishes the records
@@ -310,7 +367,17 @@ __global__ void __launch_bounds__(NT) dqn_kernel(const Args a) {
                 }
             }
         }
-        __syncthreads();      // the next step reads the new parameters, and may overwrite the records
+        if constexpr (PER) {
+            // ---- phase U: per_update_kernel's leaves and climb
+            if (wins) tr.tree[leaf] = pergpu::priority(delta, tr.epsilon, tr.alpha);
+            __syncthreads();  // the leaves are final; the next step reads the new parameters, and may overwrite the records
+            for (int d = pergpu::depth_of(2 * tr.C - 2) - 1; d >= 0; --d) {
+                if (t < n) pergpu::recompute_ancestor(tr.tree, leaf, d);
+                __syncthreads();
+            }
+        } else {
+            __syncthreads();  // the next step reads the new parameters, and may overwrite the records
+        }
     }
     if (do_apply) {
 #pragma unroll
@@ -326,6 +393,7 @@ __global__ void __launch_bounds__(NT) dqn_kernel(const Args a) {
     }
 }
 
+
 // ---- host ------------------------------------------------------------------------------------------------------------------
 thread_local std::string g_err;
 int fail(const char* what, hipError_t e = hipSuccess) {
@@ -333,6 +401,13 @@ int fail(const char* what, hipError_t e = hipSuccess) {
     if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
     else snprintf(buf, sizeof buf, "%s", what);
     g_err = buf;
+    return -1;
+}
+
+thread_local std::string g_err_per;      // mpcgpu_dqn_per_last_error
+int fail_per(const char* what, hipError_t e = hipSuccess) {
+    fail(what, e);
+    g_err_per.swap(g_err);
     return -1;
 }
 
@@ -355,7 +430,7 @@ Args base(const mpcgpu_dqn_params* p) {
 int launch(int32_t device, const Args& a, void* stream) {
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return fail("hipSetDevice", e);
-    hipLaunchKernelGGL(dqn_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(dqn_kernel<false>, dim3(1), dim3(NT), 0, (hipStream_t)stream, a, NoTree{});
     e = hipGetLastError();
     return e == hipSuccess ? 0 : fail("dqn_kernel launch", e);
 }
@@ -420,5 +495,33 @@ int32_t mpcgpu_dqn_train_dev(int32_t device, const mpcgpu_dqn_params* params, fl
 }
 
 const char* mpcgpu_dqn_last_error(void) { return dqngpu::g_err.c_str(); }
+
+// ---- include/mpcgpu_dqn_per.h -------------------------------------------------------------------------------------------------
+int32_t mpcgpu_dqn_train_per_dev(int32_t device, const mpcgpu_dqn_params* dqn, const mpcgpu_per_params* per, float* state,
+                                 double* tree, const float* buf_obs, const float* buf_next_obs, const int64_t* buf_actions,
+                                 const float* buf_rewards, const float* buf_dones, int64_t n_entries, int32_t n, int32_t K,
+                                 uint64_t seed, uint64_t serial0, float* losses, int64_t* indices, float* td, void* stream) {
+    using namespace dqngpu;
+    if (!valid(dqn)) return fail_per("invalid mpcgpu_dqn_params (lr, max_grad_norm, eps > 0, 0 <= beta < 1, double_q 0 / 1)");
+    if (!pergpu::valid(per)) return fail_per("invalid mpcgpu_per_params (capacity 1..2^30, update_max_freq >= 1, alpha, epsilon >= 0, initial_priority > 0)");
+    if (n < 1 || n > MPCGPU_DQN_MAX_ROWS) return fail_per("1 <= n <= 256");
+    if (K < 1 || K > MPCGPU_DQN_MAX_STEPS) return fail_per("1 <= K <= 65536");
+    if (n_entries < 1 || n_entries > per->capacity) return fail_per("1 <= n_entries <= capacity");
+    if (!state || !tree || !buf_obs || !buf_next_obs || !buf_actions || !buf_rewards || !buf_dones || !losses) return fail_per("null pointer");
+    Args a = base(dqn);
+    a.state = state; a.obs = buf_obs; a.next_obs = buf_next_obs; a.actions = buf_actions; a.rewards = buf_rewards;
+    a.dones = buf_dones; a.n = n; a.steps = K; a.seed = seed; a.serial0 = serial0; a.loss = losses; a.td = td;
+    a.mode = DO_GRAD | DO_APPLY;
+    PerArgs tr{};
+    tr.tree = tree; tr.indices = indices; tr.C = per->capacity; tr.n_entries = n_entries;
+    tr.alpha = per->alpha; tr.beta = per->beta; tr.epsilon = per->epsilon;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_per("hipSetDevice", e);
+    hipLaunchKernelGGL(dqn_kernel<true>, dim3(1), dim3(NT), 0, (hipStream_t)stream, a, tr);
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail_per("dqn_kernel<PER> launch", e);
+}
+
+const char* mpcgpu_dqn_per_last_error(void) { return dqngpu::g_err_per.c_str(); }
 
 }  // extern "C"

@@ -20,7 +20,7 @@
 #include <string>
 
 #include "../../include/mpcgpu_per.h"
-#include "per_pow.hpp"
+#include "per_tree.hpp"
 
 namespace pergpu {
 
@@ -32,13 +32,8 @@ constexpr int SMALL = 1024;            // threads of the one-workgroup kernels
 // marks the leaves of an update while the rows settle which of them wins
 constexpr unsigned long long TAG = 0xFFF8000000000000ull;
 
-// x^y as the C library rounds it (per_pow.hpp); outside the range a priority or a weight can have, the device library's
-__device__ inline double pow_as_libm(double x, double y) {
-    double v;
-    return libm_pow(x, y, &v) ? v : pow(x, y);
-}
-
-__host__ __device__ inline int depth_of(int64_t i) { return 63 - __builtin_clzll((unsigned long long)(i + 1)); }
+// pow_as_libm, depth_of, the descent, the weight, the priority and the recomputation of one ancestor: per_tree.hpp (shared with
+// the prioritized K-step launch of dqngpu.hip)
 
 // up to four contiguous leaf ranges (ring wrap x two leaf depths), each on ONE depth
 struct Ranges {
@@ -146,7 +141,7 @@ __global__ void __launch_bounds__(SMALL) per_update_kernel(double* tree, int64_t
         const int64_t idx = indices[r];
         if (idx >= C - 1 && idx <= 2 * C - 2 &&
             __hip_atomic_load(&bits[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (TAG | (unsigned long long)r))
-            tree[idx] = pow_as_libm(fabs((double)td[r]) + epsilon, alpha);
+            tree[idx] = priority(td[r], epsilon, alpha);
     }
     __syncthreads();
     const int D = depth_of(2 * C - 2);
@@ -154,10 +149,7 @@ __global__ void __launch_bounds__(SMALL) per_update_kernel(double* tree, int64_t
         for (int r = threadIdx.x; r < n; r += SMALL) {
             const int64_t idx = indices[r];
             if (idx < C - 1 || idx > 2 * C - 2) continue;
-            const int dl = depth_of(idx);
-            if (dl <= d) continue;
-            const int64_t node = ((idx + 1) >> (dl - d)) - 1;
-            tree[node] = tree[2 * node + 1] + tree[2 * node + 2];
+            recompute_ancestor(tree, idx, d);
         }
         __syncthreads();
     }
@@ -170,27 +162,16 @@ __global__ void __launch_bounds__(SMALL) per_sample_kernel(const double* tree, i
     constexpr int PER_THREAD = MPCGPU_PER_MAX_ROWS / SMALL;
     const int64_t len = 2 * C - 1;
     const double total = tree[0];
-    const double segment = total / (double)n;
     double w[PER_THREAD];
     double wmax = -INFINITY;
     for (int j = 0; j < PER_THREAD; ++j) {
         const int i = threadIdx.x + j * SMALL;
         w[j] = 0.0;
         if (i >= n) continue;
-        const double a = segment * (double)i, b = segment * (double)(i + 1);
-        double s = a + (b - a) * u[i];
-        int64_t idx = 0;
-        for (int64_t left = 1; left < len; left = 2 * idx + 1) {
-            const double tl = tree[left], tr = tree[left + 1];
-            bool go_left = s <= tl;
-            if (go_left && tl == 0.0) go_left = false;          // never into an empty subtree: the sibling instead
-            else if (!go_left && tr == 0.0) go_left = true;
-            if (go_left) idx = left;
-            else { s = s - tl; idx = left + 1; }
-        }
+        const int64_t idx = descend(tree, len, stratum_point(total, n, i, u[i]));
         indices[i] = idx;
         positions[i] = idx - (C - 1);
-        w[j] = pow_as_libm((double)n_entries * tree[idx] / total, -beta);
+        w[j] = raw_weight(n_entries, tree[idx], total, beta);
         wmax = w[j] > wmax ? w[j] : wmax;
     }
     red[threadIdx.x] = wmax;
@@ -219,11 +200,6 @@ int fail(const char* what, hipError_t e = hipSuccess) {
     else snprintf(buf, sizeof buf, "%s", what);
     g_err = buf;
     return -1;
-}
-
-bool valid(const mpcgpu_per_params* p) {
-    return p && p->capacity >= 1 && p->capacity <= ((int64_t)1 << 30) && p->update_max_freq >= 1 && p->alpha >= 0.0 &&
-           p->epsilon >= 0.0 && p->initial_priority > 0.0;
 }
 
 int begin(int32_t device, const mpcgpu_per_params* p) {

@@ -240,6 +240,12 @@ class FusedDqnTrainer(DqnTrainerBase):
             done += part
         return losses
 
+    def train_per(self, buffer, k: int, batch_size: int) -> torch.Tensor:
+        """:meth:`train` on a PRIORITIZED buffer: sample from its sum tree, weighted step, priorities written back, ``k`` times
+        in one launch (:func:`dqn_per_fused.train_per`)."""
+        from .dqn_per_fused import train_per
+        return train_per(self, buffer, k, batch_size)
+
     def sync_target(self) -> None:
         """Hard target update: a copy of 1 177 floats inside the state block."""
         with torch.no_grad():

@@ -385,7 +385,7 @@ class DqnLearner:
                  target_update_interval: int = 10_000, exploration_fraction: float = 0.2,
                  exploration_initial_eps: float = 1.0, exploration_final_eps: float = 0.05, seed: int = 0,
                  use_graph: bool = False, track_episodes: bool = True, per: bool = False,
-                 per_kwargs: Optional[Dict] = None, fused: bool = False):
+                 per_kwargs: Optional[Dict] = None, fused: bool = False, per_in_kernel: bool = False):
         """``per=True``: prioritized experience replay (the reference's ``'per': True``): the buffer keeps a sum tree of
         priorities (``per_kwargs``: alpha, beta, epsilon, update_max_freq, initial_priority), minibatches are drawn by
         priority, the loss is weighted by the importance weights and the drawn rows are re-prioritized with their TD errors
@@ -394,7 +394,14 @@ class DqnLearner:
         ``fused=True`` (ray environment only): the update is the fused HIP kernel of :class:`dqn_fused.FusedDqnTrainer`
         (DESIGN.md 8.6).  With uniform replay and one rank the whole update round of ``learn`` is ONE launch that draws its
         own minibatches from the counter stream ``(seed + rank, serial)`` -- both are part of ``state_dict`` --; with
-        ``per=True`` or several ranks it is one fused update per step around the tree's kernels or the all-reduce."""
+        ``per=True`` or several ranks it is one fused update per step around the tree's kernels or the all-reduce.
+
+        ``per_in_kernel=True`` (needs ``fused=True`` and ``per=True``, one rank): the round is ONE launch with prioritized
+        replay too -- the kernel samples the tree, updates and re-prioritises step after step
+        (:meth:`dqn_fused.FusedDqnTrainer.train_per`), its uniforms from the same counter stream.  The
+        checkpoint has the same keys either way and moves between the two settings."""
+        if per_in_kernel and not (fused and per):
+            raise ValueError("per_in_kernel=True needs fused=True and per=True: it is the prioritized form of the fused K-step launch")
         self.env, self.device = env, env.device
         self.image = bool(getattr(env, "is_image_env", False))
         if self.image and use_graph:
@@ -430,9 +437,14 @@ class DqnLearner:
         self.ep_count, self.ep_return_sum, self.ep_success_sum = (torch.zeros((), dtype=torch.float64, device=self.device) for _ in range(3))
         if use_graph:
             self.trainer.enable_graph(batch_size, weighted=self.per)
-        # decided once: one step's update, and whether a round is ONE launch that samples the buffer itself (fused, uniform, one rank)
+        # decided once: one step's update, and whether a round is ONE launch that samples the buffer itself (fused, one rank, uniform or per_in_kernel)
         self._update = self.trainer.update_graphed if use_graph else self.trainer.update
-        self._one_launch = self.fused and not self.per and not self.trainer.collective
+        self.per_in_kernel = bool(per_in_kernel)
+        if self.per_in_kernel and self.trainer.collective:
+            raise ValueError("per_in_kernel=True is the one-rank path: several ranks (or force_collective) update step by step "
+                             "around the all-reduce")
+        self._one_launch = self.fused and (not self.per or self.per_in_kernel) and not self.trainer.collective
+        self._train = self.trainer.train_per if self.per_in_kernel else getattr(self.trainer, "train", None)
         # state of the collection loop between two learn() calls (a run can be checkpointed and resumed in the middle)
         self._obs, self._ep_return, self.n_updates = None, None, 0
         self._last_loss = torch.zeros((), device=self.device)
@@ -539,7 +551,7 @@ class DqnLearner:
             if self.num_timesteps > self.learning_starts and self.buffer.size >= self.batch_size:
                 steps = self.gradient_steps if self.gradient_steps >= 0 else collected
                 if self._one_launch and steps > 0:
-                    last_loss = self.trainer.train(self.buffer, steps, self.batch_size)[-1]
+                    last_loss = self._train(self.buffer, steps, self.batch_size)[-1]
                 for _ in range(0 if self._one_launch else steps):
                     batch = self.buffer.sample(self.batch_size, self.gen)
                     last_loss = self._update(batch)       # eager, a replayed graph or the fused kernel: bound in __init__
