@@ -17,7 +17,9 @@
  * All pointers are DEVICE pointers.  Every call enqueues its kernels on `stream` and returns: none synchronises,
  * allocates or copies to the host, so all of them can be captured into a graph (sizes, positions and n_entries are baked
  * into a captured call like any other kernel argument).  Plain pointers and sizes, no ownership taken, no exceptions:
- * 0 = ok, < 0 = error (text via mpcgpu_per_last_error, thread-local).  There is no CPU fallback.
+ * 0 = ok, < 0 = error (text via mpcgpu_per_last_error, thread-local).  Every call checks the parameters first and refuses,
+ * before it touches the device, what the comments of mpcgpu_per_params exclude (a NaN is excluded everywhere).  There is no CPU
+ * fallback.
  */
 #ifndef MPCGPU_PER_H
 #define MPCGPU_PER_H
@@ -33,9 +35,9 @@ extern "C" {
 typedef struct mpcgpu_per_params {
     int64_t capacity;          /* 1 .. 2^30 */
     int64_t update_max_freq;   /* >= 1: max_p is re-read at the start of an add call once this many rows were added since */
-    double alpha;              /* priority = (|td| + epsilon)^alpha, 0.3 */
-    double beta;               /* weight = (n_entries * p / total)^-beta, 0.4 */
-    double epsilon;            /* 1e-3 */
+    double alpha;              /* >= 0: priority = (|td| + epsilon)^alpha, 0.3 */
+    double beta;               /* >= 0 and finite (0: every weight is 1): weight = (n_entries * p / total)^-beta, 0.4 */
+    double epsilon;            /* >= 0, 1e-3 */
     double initial_priority;   /* max_p of an empty buffer, 1 */
 } mpcgpu_per_params;
 

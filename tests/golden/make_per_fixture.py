@@ -2,6 +2,7 @@
 """Golden trace of the reference's own prioritized replay buffer.
 
 Run in the build container only (needs /root/reference):   python tests/golden/make_per_fixture.py
+                                                           python tests/golden/make_per_fixture.py NAME   (a row of SETTINGS)
 
 The reference's ``PerReplayBuffer`` (src/pkg_dqn/utils/per_dqn.py:25-187) is loaded from the reference tree at run time
 and executed on a seeded schedule of adds, samples and re-prioritizations.  stable_baselines3 and gym are not installed;
@@ -17,7 +18,8 @@ weights, the TD errors; every 20 steps the leaves, tree[0] and the reference's o
 tree[0].  ``tolerance`` = ten times the largest drift: how far the reference is from its own exact sum, with a margin.
 A draw is DECIDABLE when its s lies further than tolerance * tree[0] from every leaf boundary of the exact prefix sums;
 the script refuses to write a trace with an undecidable draw (change SEED if it ever trips).
-Only data is written: per_trace.npz.
+Only data is written: per_trace.npz, or the file of the named row of SETTINGS -- the same schedule and SEED at other settings
+of the buffer (the ones most users take from the literature, and the corners alpha = 1 / beta = 0 / initial_priority != 1).
 """
 import importlib.util
 import io
@@ -36,6 +38,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SEED = 20261016
 CAPACITY, FREQ, N_SAMPLE = 300, 100, 32
 SINGLE_CALLS, QUAD_CALLS, CHECK_EVERY = 60, 180, 20
+# name -> (file, keyword arguments of the reference's PerReplayBuffer); "default" passes none, as the script always did
+SETTINGS = {
+    "default": ("per_trace.npz", {}),
+    "a06_b10_e1e-6": ("per_trace_a06_b10_e1e-6.npz", dict(alpha=0.6, beta=1.0, epsilon=1e-6)),
+    "a10_b00_e1e-2_p25": ("per_trace_a10_b00_e1e-2_p25.npz", dict(alpha=1.0, beta=0.0, epsilon=1e-2, initial_priority=2.5)),
+}
 
 
 class _DictReplayBuffer:
@@ -104,7 +112,8 @@ def savez_deterministic(path, **arrays):
             zf.writestr(info, buf.getvalue())
 
 
-def main():
+def main(name="default"):
+    file, settings = SETTINGS[name]
     PerReplayBuffer = load_reference_class()
     rng = np.random.default_rng(SEED)
     drawn = []
@@ -124,7 +133,7 @@ def main():
     ck_step, ck_leaves, ck_total, ck_drift = [], [], [], []
     repeated = 0
     for step, rows in enumerate(rows_of):
-        buf = PerReplayBuffer(CAPACITY, None, None, "cpu", n_envs=rows, update_max_freq=FREQ) if step == 0 else buf
+        buf = PerReplayBuffer(CAPACITY, None, None, "cpu", n_envs=rows, update_max_freq=FREQ, **settings) if step == 0 else buf
         buf._n_envs = rows
         out["pos"][step] = buf.pos
         empty = {"x": np.zeros((rows, 1))}
@@ -161,13 +170,13 @@ def main():
     assert tolerance > 0.0
     assert out["margin"].min() > tolerance, ("undecidable draw: change SEED", out["margin"].min(), tolerance)
     assert repeated > 0, "no repeated index in any sample: the last-row-wins rule is not exercised"
-    savez_deterministic(os.path.join(HERE, "per_trace.npz"), capacity=CAPACITY, update_max_freq=FREQ, alpha=buf.alpha,
+    savez_deterministic(os.path.join(HERE, file), capacity=CAPACITY, update_max_freq=FREQ, alpha=buf.alpha,
                         beta=buf.beta, epsilon=buf.epsilon, initial_priority=float(buf.initial_priority),
                         ck_step=np.array(ck_step), ck_leaves=np.array(ck_leaves), ck_total=np.array(ck_total),
                         ck_drift=np.array(ck_drift), tolerance=tolerance, **out)
-    print(f"per_trace.npz: {S} steps, {S * N_SAMPLE} draws, {repeated} repeated indices, largest drift {max(ck_drift):.3e}, "
+    print(f"{file}: {S} steps, {S * N_SAMPLE} draws, {repeated} repeated indices, largest drift {max(ck_drift):.3e}, "
           f"tolerance {tolerance:.3e}, smallest margin {out['margin'].min():.3e}")
 
 
 if __name__ == "__main__":
-    main()
+    main(*sys.argv[1:2])

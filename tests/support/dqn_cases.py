@@ -9,6 +9,29 @@ from . import dqn_numpy as tw
 
 F = np.float32
 SIZES = (1, 2, 31, 32, 33, 63, 64, 65, 255, 256)
+# name -> keyword arguments of dqn_numpy.Twin that leave their defaults (lr 1e-4, gamma 0.98, max_grad_norm 10, betas 0.9 / 0.999,
+# eps 1e-8): every field of mpcgpu_dqn_params on both sides of its default and at the ends of its range
+PARAMETER_SETS = {
+    "gamma_0": dict(gamma=0.0),
+    "gamma_0.5": dict(gamma=0.5),
+    "gamma_1": dict(gamma=1.0),
+    "lr_1e-2": dict(lr=1e-2),
+    "lr_1e-6": dict(lr=1e-6),
+    "clip_1e-3": dict(max_grad_norm=1e-3),            # the clip bites on every step
+    "clip_1e6": dict(max_grad_norm=1e6),              # ... and never
+    "beta1_0": dict(beta1=0.0),
+    "beta2_0": dict(beta2=0.0),
+    "betas_0": dict(beta1=0.0, beta2=0.0),
+    "betas_0.5_0.9": dict(beta1=0.5, beta2=0.9),
+    "betas_0.99_0.9999": dict(beta1=0.99, beta2=0.9999),
+    "eps_1e-3": dict(eps=1e-3),
+    "eps_1e-12": dict(eps=1e-12),
+    "all_moved": dict(lr=3e-3, gamma=0.9, max_grad_norm=0.5, beta1=0.8, beta2=0.99, eps=1e-4, double_q=True),
+}
+
+
+def moves_a_beta(kw) -> bool:
+    return "beta1" in kw or "beta2" in kw
 
 
 def random_theta(rng) -> np.ndarray:
@@ -124,8 +147,8 @@ def torch_batch(batch, dtype=None, device="cpu"):
     return out
 
 
-def torch_gradient(theta, target, batch, double_q=False, dtype=None, device="cpu"):
-    """Flat gradient of the trainer's own loss by autograd, as float64 numpy."""
-    tr = torch_trainer(theta, target, double_q, dtype, device)
+def torch_gradient(theta, target, batch, double_q=False, dtype=None, device="cpu", **kw):
+    """Flat gradient of the trainer's own loss by autograd, as float64 numpy (``kw``: gamma)."""
+    tr = torch_trainer(theta, target, double_q, dtype, device, **kw)
     tr._backward(torch_batch(batch, dtype, device))
     return np.concatenate([p.grad.detach().double().cpu().numpy().reshape(-1) for p in tr.q_net.parameters()])

@@ -81,6 +81,22 @@ def test_twin_gradient_on_random_batches(n):
         assert mine <= 4.0 * E
 
 
+@pytest.mark.parametrize("name", sorted(dqn_cases.PARAMETER_SETS))
+def test_twin_gradient_at_every_parameter_set(name):
+    """The same criterion off the default gamma = 0.98 (and with the set's double_q): 33 rows with weights."""
+    kw = dqn_cases.PARAMETER_SETS[name]
+    gamma, double_q = kw.get("gamma", 0.98), kw.get("double_q", False)
+    rng = np.random.default_rng(700)
+    theta, target, b = dqn_cases.random_theta(rng), dqn_cases.random_theta(rng), dqn_cases.random_batch(rng, 33, weights=True)
+    exact = dqn_cases.torch_gradient(theta, target, b, double_q, dtype=torch.float64, gamma=gamma)
+    eager = dqn_cases.torch_gradient(theta, target, b, double_q, dtype=torch.float32, gamma=gamma)
+    twin = tw.Twin(theta, target, **kw)
+    mine = twin.grad(b["obs"], b["next_obs"], b["actions"], b["rewards"], b["dones"], b["weights"])[0]
+    E, mine = float(np.abs(eager - exact).max()), float(np.abs(mine.astype(np.float64) - exact).max())
+    print(f"{name}: eager float32 off by E = {E:.3e}, twin by {mine:.3e} (ratio {mine / E:.2f})")
+    assert mine <= 4.0 * E
+
+
 def test_the_edge_batches_are_what_they_claim():
     def run(name):
         c, b = EDGE[name], EDGE[name]["batch"]
@@ -131,6 +147,81 @@ def test_twin_adam_step(t, gscale):
     worst = float(np.max(np.abs(new.astype(np.float64) - exact) / bound))
     print(f"t = {t}, |g| ~ {gscale:g}: worst |d theta| / bound = {worst:.3f}")
     assert worst <= 1.0
+
+
+def adam_step_bound(theta, m, v, t, g, lr=1e-4, max_norm=10.0, b1=0.9, b2=0.999, eps=1e-8):
+    """First-order bound on |twin - float64| of the new theta, term by term.  e = 2^-24 (one float32 rounding, relative); every
+    quantity on the right is the float64 one.
+
+    the clip   sum of squares (include/mpcgpu_dqn.h): 1177 squares, e each; a lane adds its 5 squares from 0 (4 roundings);
+               the 256 lane sums fold in 8 halvings (8 roundings); all terms are positive, so the sum is off by <= 13 e.
+               sqrt halves that and rounds: 7.5 e.  + 1e-6 (the constant's own rounding, and the addition's): 2 e.
+               max_grad_norm rounded to float32, and the division: 2 e.  So coef = ratio carries dc <= 11.5 e WHEN THE CLIP IS
+               ACTIVE -- one common factor (1 + dc) on every entry of g; coef = 1 is exact when it is idle (dc = 0).  Where the
+               float64 ratio is within dc of 1 the two may decide differently, and coef is again within dc of the float64 one.
+               g' = g * coef: one more rounding.
+    m          m' = b1 m + (1 - b1) g'.  With A = |b1 m|, B = |(1 - b1) g'|:  beta rounded (e) and the product (e) on A;
+               1 - beta rounded (e), the product (e), g' = g coef (e) and dc on B; the addition e |m'|:
+               |dm| <= 2 e A + (3 e + dc) B + e |m'|.   Where A and B cancel, |m'| and with it |u| is small and |dm| is not:
+               this is the term the bound 2^-23 (|theta| + 8 |u|) has no room for once lr / D is not small against |theta|.
+    v          v' = b2 v + (1 - b2) g'^2, all terms positive: the same roundings plus the square's, and 2 dc:
+               |dv| / v' <= 2 dc + 6 e.
+    D          D = sqrt(v') / root + eps: sqrt halves dv and rounds (dc + 4 e), root = float32(sqrt(bc2)) (e), the division
+               (e), eps rounded and the addition (2 e at most):  |dD| / D <= dc + 8 e.
+    u          u = step * (m' / D), step = float32(lr / bc1) (e), the division (e), the product (e):
+               |du| <= (step / D) |dm| + |u| (dc + 11 e).
+    theta      theta' = theta - u rounds once: e (|theta| + |u|).
+    Together   |d theta'| <= e |theta| + |u| (dc + 13 e) + (step / D) (2 e A + (3 e + dc) B).
+    """
+    e = 2.0 ** -24
+    theta, m, v, g = (np.asarray(x, np.float64) for x in (theta, m, v, g))
+    ratio = max_norm / (np.sqrt(np.sum(g * g)) + 1e-6)
+    dc = 11.5 * e if ratio < 1.0 + 11.5 * e else 0.0
+    g = g * min(1.0, ratio)
+    t = t + 1
+    A, B = np.abs(b1 * m), np.abs((1 - b1) * g)
+    m1 = b1 * m + (1 - b1) * g
+    v1 = b2 * v + (1 - b2) * g * g
+    D = np.sqrt(v1) / np.sqrt(1 - b2 ** t) + eps
+    step = lr / (1 - b1 ** t)
+    u = step * m1 / D
+    return e * np.abs(theta) + np.abs(u) * (dc + 13 * e) + (step / D) * (2 * e * A + (3 * e + dc) * B)
+
+
+# the sets at which 2^-23 (|theta| + 8 |u|) is NOT a bound: lr / D is no longer small against |theta| (see adam_step_bound)
+SIMPLE_BOUND_FAILS = {"lr_1e-2"}
+
+
+@pytest.mark.parametrize("name", sorted(dqn_cases.PARAMETER_SETS))
+def test_twin_adam_step_at_every_parameter_set(name):
+    """``dqn_numpy.apply`` against float64 Adam (the yardstick) with the set's parameters, at t = 0 (fresh moments), 999 and 10^6
+    and gradients of four scales: within the bound of test_twin_adam_step where that holds, and everywhere within the bound
+    restated term by term in :func:`adam_step_bound`."""
+    kw = {k: v for k, v in dqn_cases.PARAMETER_SETS[name].items() if k not in ("gamma", "double_q")}
+    f64 = dict(lr=kw.get("lr", 1e-4), max_norm=kw.get("max_grad_norm", 10.0), b1=kw.get("beta1", 0.9), b2=kw.get("beta2", 0.999),
+               eps=kw.get("eps", 1e-8))
+    worst_simple = worst_full = 0.0
+    for t in (0, 999, 10 ** 6):
+        for gscale in (0.0, 1e-4, 1.0, 1e3):
+            rng = np.random.default_rng(7 + t % 1000)
+            theta = dqn_cases.random_theta(rng)
+            g = (gscale * rng.standard_normal(tw.NP)).astype(F)
+            g[::7] = 0.0
+            fresh = t == 0
+            m = np.zeros(tw.NP, F) if fresh else (0.1 * rng.standard_normal(tw.NP)).astype(F)
+            v = np.zeros(tw.NP, F) if fresh else (rng.random(tw.NP) ** 4).astype(F)
+            if not fresh:
+                m[::7], v[::7] = 0.0, 0.0
+            new, m1, v1, t1 = tw.apply(theta, m, v, t, g, **kw)
+            exact, u = adam_float64(theta, m, v, t, g, **f64)
+            assert t1 == t + 1 and np.array_equal(new[::7], theta[::7])
+            err = np.abs(new.astype(np.float64) - exact)
+            worst_simple = max(worst_simple, float(np.max(err / (2.0 ** -23 * (np.abs(theta.astype(np.float64)) + 8.0 * np.abs(u))))))
+            worst_full = max(worst_full, float(np.max(err / adam_step_bound(theta, m, v, t, g, **f64))))
+    print(f"{name}: worst |d theta| / (2^-23 (|theta| + 8 |u|)) = {worst_simple:.3f}, / the restated bound = {worst_full:.3f}")
+    assert worst_full <= 1.0
+    if name not in SIMPLE_BOUND_FAILS:
+        assert worst_simple <= 1.0
 
 
 # ---- sampling ---------------------------------------------------------------------------------------------------------------

@@ -82,7 +82,10 @@ def test_refusals_of_the_entry_need_no_device():
     cases = ((dict(n=0), "1 <= n <= 256"), (dict(n=257), "1 <= n <= 256"), (dict(K=0), "1 <= K <= 65536"), (dict(K=65537), "1 <= K <= 65536"),
              (dict(n_entries=0), "1 <= n_entries <= capacity"), (dict(n_entries=101), "1 <= n_entries <= capacity"),
              (dict(tree=None), "null pointer"), (dict(dqn=dqn_fused._CDqnParams(0.0, 0.98, 10.0, 0.9, 0.999, 1e-8, 0, 0)), "mpcgpu_dqn_params"),
-             (dict(per=per_tree._CPerParams(0, 1000, 0.3, 0.4, 1e-3, 1.0)), "mpcgpu_per_params"))
+             (dict(per=per_tree._CPerParams(0, 1000, 0.3, 0.4, 1e-3, 1.0)), "mpcgpu_per_params"),
+             (dict(per=per_tree._CPerParams(100, 1000, 0.3, float("nan"), 1e-3, 1.0)), "mpcgpu_per_params (capacity"),
+             (dict(per=per_tree._CPerParams(100, 1000, 0.3, -0.4, 1e-3, 1.0)), "0 <= beta < inf"),
+             (dict(per=per_tree._CPerParams(100, 1000, 0.3, float("inf"), 1e-3, 1.0)), "0 <= beta < inf"))
     for kw, text in cases:
         assert call(**kw) < 0 and text in lib.mpcgpu_dqn_per_last_error().decode(), kw
 

@@ -31,6 +31,16 @@ def make(theta, target, double_q=False, **kw):
     return tr
 
 
+def make_set(theta, target, kw, **more):
+    """A trainer at a set of tests/support/dqn_cases.py PARAMETER_SETS: lr, gamma, max_grad_norm and double_q are keywords of
+    ``FusedDqnTrainer``; beta1, beta2 and eps are fields of its ``params`` (what every entry passes to the library)."""
+    tr = make(theta, target, **{k: v for k, v in kw.items() if k in ("lr", "gamma", "max_grad_norm", "double_q")}, **more)
+    for k in ("beta1", "beta2", "eps"):
+        if k in kw:
+            setattr(tr.params, k, kw[k])
+    return tr
+
+
 def on_device(batch):
     return {k: torch.from_numpy(v).to(DEV) for k, v in batch.items()}
 
@@ -51,14 +61,18 @@ def assert_state_is(tr, twin):
     assert tr.step_count == twin.t
 
 
-def walk(theta, target, batches, double_q=False, t0=None):
+def walk(theta, target, batches, double_q=False, t0=None, kw=None):
     """Every batch through (a) grad_dev then apply_dev, (b) step_dev and (c) the twin: gradient, loss, delta after the gradient,
-    parameters, moments and step count after the step, all bit for bit; (a) and (b) also against each other."""
-    two, one, twin = make(theta, target, double_q), make(theta, target, double_q), tw.Twin(theta, target, double_q=double_q)
+    parameters, moments and step count after the step, all bit for bit; (a) and (b) also against each other.  ``kw``: a set of
+    dqn_cases.PARAMETER_SETS (the defaults otherwise)."""
+    kw = dict(kw or {}, double_q=(kw or {}).get("double_q", double_q))
+    two, one, twin = make_set(theta, target, kw), make_set(theta, target, kw), tw.Twin(theta, target, **kw)
     if t0 is not None:          # a checkpoint: moments and a step count in the form of Adam's state_dict
         rng = np.random.default_rng(1)
         twin.m, twin.v, twin.t = (0.1 * rng.standard_normal(NP)).astype(F), (rng.random(NP) ** 4).astype(F), t0
-        sd = dqn_fused.adam_state_dict(torch.from_numpy(twin.m), torch.from_numpy(twin.v), t0, dqn_fused.adam_groups(1e-4))
+        groups = dqn_fused.adam_groups(two.params.lr)
+        groups[0].update(betas=(two.params.beta1, two.params.beta2), eps=two.params.eps)
+        sd = dqn_fused.adam_state_dict(torch.from_numpy(twin.m), torch.from_numpy(twin.v), t0, groups)
         two.load_optimizer_state(sd); one.load_optimizer_state(sd)
         assert_state_is(two, twin)
     for batch in batches:
@@ -98,6 +112,81 @@ def test_step_counts_one_and_a_million(t0):
     rng = np.random.default_rng(77)
     twin = walk(dqn_cases.random_theta(rng), dqn_cases.random_theta(rng), [dqn_cases.random_batch(rng, 32)], t0=t0 or None)
     assert twin.t == t0 + 1
+
+
+@pytest.mark.parametrize("name", sorted(dqn_cases.PARAMETER_SETS))
+def test_every_parameter_set_equals_the_twin(name):
+    """Two batches of 33 rows, the second with weights, at every set of the table: from t = 0 and, where a beta moved, from
+    checkpoints at t = 999 and t = 10^6 (there beta^t leaves the restated pow's range: 0.5^999 and every beta^(10^6) but
+    0.9999^(10^6) go through the device library's pow, the latter to an underflow)."""
+    kw = dqn_cases.PARAMETER_SETS[name]
+    for t0 in (None, 999, 10 ** 6) if dqn_cases.moves_a_beta(kw) else (None,):
+        rng = np.random.default_rng(300)
+        batches = [dqn_cases.random_batch(rng, 33), dqn_cases.random_batch(rng, 33, weights=True)]
+        twin = walk(dqn_cases.random_theta(rng), dqn_cases.random_theta(rng), batches, t0=t0, kw=kw)
+        assert twin.t == (t0 or 0) + 2
+        print(f"{name}, t0 = {t0 or 0}: gradient, loss, delta, theta, m, v and t equal the twin's bit for bit (0 differing bits)")
+
+
+def test_all_moved_train_equals_single_steps_and_the_twin():
+    """``train`` with K = 3, n = 32 on 33 rows at the set that moves everything: against single steps and the twin's loop."""
+    kw = dqn_cases.PARAMETER_SETS["all_moved"]
+    K, n, size = 3, 32, 33
+    rng = np.random.default_rng(K + size + n)
+    theta, target = dqn_cases.random_theta(rng), dqn_cases.random_theta(rng)
+    buf, host = make_buffer(rng, size, capacity=size + 7)
+    seed, serial0 = 2 ** 63 + 11, 2 ** 40 + 5
+    fused, steps = make_set(theta, target, kw, seed=seed), make_set(theta, target, kw)
+    fused.serial = serial0
+    losses = fused.train(buf, K, n)
+    assert fused.serial == serial0 + K and fused.num_updates == K and losses.shape == (K,)
+    want = []
+    for s in range(K):
+        rows = torch.from_numpy(tw.sample_rows(seed, serial0 + s, n, size)).to(DEV)
+        want.append(steps.update(buf._rows(rows)).clone())
+    assert torch.equal(fused.state, steps.state) and fused.step_count == K
+    assert same(losses, torch.stack(want))
+    twin = tw.Twin(theta, target, **kw)
+    assert same(losses, twin.train(host, size, n, K, seed, serial0))
+    assert_state_is(fused, twin)
+
+
+def test_invalid_parameters_are_refused_and_leave_the_state_alone():
+    """Every rule of mpcgpu_dqn_params through the C ABI, on all four entries: the text names the structure and its rules, and
+    neither the state block nor an output is written."""
+    rng = np.random.default_rng(5)
+    theta = dqn_cases.random_theta(rng)
+    tr = make(theta, theta)
+    buf, _ = make_buffer(rng, 64)
+    b = on_device(dqn_cases.random_batch(rng, 8))
+    tr.update(b)                                                             # a state with moments in it
+    before, outs = tr.state.clone(), (tr._bucket.clone(), tr._loss.clone(), tr._td.clone())
+    lib, losses, st = tr._lib, torch.zeros(4, device=DEV), torch.cuda.current_stream().cuda_stream
+    good = dict(lr=1e-4, gamma=0.98, max_grad_norm=10.0, beta1=0.9, beta2=0.999, eps=1e-8, double_q=0)
+    bad = [dict(lr=0.0), dict(lr=-1e-4), dict(lr=float("nan")), dict(max_grad_norm=0.0), dict(max_grad_norm=-1.0), dict(eps=0.0),
+           dict(eps=-1e-8), dict(beta1=1.0), dict(beta1=-0.1), dict(beta2=1.0), dict(beta2=-0.1), dict(beta2=float("nan")),
+           dict(double_q=2), dict(double_q=-1)]
+    for change in bad:
+        f = dict(good, **change)
+        p = dqn_fused._CDqnParams(f["lr"], f["gamma"], f["max_grad_norm"], f["beta1"], f["beta2"], f["eps"], f["double_q"], 0)
+        mini = (b["obs"].data_ptr(), b["next_obs"].data_ptr(), b["actions"].data_ptr(), b["rewards"].data_ptr(), b["dones"].data_ptr(), None,
+                8, tr._bucket.data_ptr(), tr._loss.data_ptr(), tr._td.data_ptr(), st)
+        calls = (lambda: lib.mpcgpu_dqn_grad_dev(0, C.byref(p), tr.state.data_ptr(), *mini),
+                 lambda: lib.mpcgpu_dqn_step_dev(0, C.byref(p), tr.state.data_ptr(), *mini),
+                 lambda: lib.mpcgpu_dqn_apply_dev(0, C.byref(p), tr.state.data_ptr(), tr._bucket.data_ptr(), 1.0, st),
+                 lambda: lib.mpcgpu_dqn_train_dev(0, C.byref(p), tr.state.data_ptr(), buf.obs.data_ptr(), buf.next_obs.data_ptr(),
+                                                  buf.actions.data_ptr(), buf.rewards.data_ptr(), buf.dones.data_ptr(), 64, 8, 2, 1, 0,
+                                                  losses.data_ptr(), st))
+        for call in calls:
+            lib.mpcgpu_dqn_grad_dev(0, C.byref(tr.params), tr.state.data_ptr(), *mini[:6], 0, *mini[7:])    # another text in between
+            assert "1 <= n <= 256" in lib.mpcgpu_dqn_last_error().decode()
+            assert call() < 0, change
+            text = lib.mpcgpu_dqn_last_error().decode()
+            assert "invalid mpcgpu_dqn_params" in text and "lr, max_grad_norm, eps > 0" in text and "0 <= beta < 1" in text \
+                and "double_q 0 / 1" in text, (change, text)
+    torch.cuda.synchronize()
+    assert torch.equal(tr.state, before) and all(torch.equal(x, y) for x, y in zip((tr._bucket, tr._loss, tr._td), outs))
+    assert not losses.any() and tr.step_count == 1
 
 
 def test_scaled_apply_equals_the_twin():

@@ -36,11 +36,20 @@ def same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
 
 
-def make_buffer(rng, capacity, rows, chunk=None, prime=3, reward_scale=1.0, obs_scale=1.0, terminal=False):
+def make_set(theta, target, kw, **more):
+    """A trainer at a set of dqn_cases.PARAMETER_SETS (beta1, beta2 and eps are fields of ``params``, see test_gpu_dqn_fused.py)."""
+    tr = make(theta, target, **{k: v for k, v in kw.items() if k in ("lr", "gamma", "max_grad_norm", "double_q")}, **more)
+    for k in ("beta1", "beta2", "eps"):
+        if k in kw:
+            setattr(tr.params, k, kw[k])
+    return tr
+
+
+def make_buffer(rng, capacity, rows, chunk=None, prime=3, reward_scale=1.0, obs_scale=1.0, terminal=False, per_kwargs=None):
     """A prioritized ``ReplayBuffer`` of ``capacity`` that took ``rows`` transitions through ``add`` (more than ``capacity``: the
     ring wrapped), and whose priorities then went through ``prime`` rounds of sample / update so that they differ (0: a fresh
     buffer, every leaf equal to max_p)."""
-    buf = dqn_train.ReplayBuffer(capacity, 46, torch.device(DEV), per_kwargs={})
+    buf = dqn_train.ReplayBuffer(capacity, 46, torch.device(DEV), per_kwargs=dict(per_kwargs or {}))
     left = rows
     while left > 0:
         m = min(left, chunk or capacity)
@@ -56,9 +65,9 @@ def make_buffer(rng, capacity, rows, chunk=None, prime=3, reward_scale=1.0, obs_
     return buf
 
 
-def clone(buf):
+def clone(buf, per_kwargs=None):
     """A second buffer with the same rows, tree and ring position."""
-    other = dqn_train.ReplayBuffer(buf.capacity, 46, torch.device(DEV), per_kwargs={})
+    other = dqn_train.ReplayBuffer(buf.capacity, 46, torch.device(DEV), per_kwargs=dict(per_kwargs or {}))
     for k in FIELDS:
         getattr(other, k).copy_(getattr(buf, k))
     other.sum_tree.tree.copy_(buf.sum_tree.tree)
@@ -86,7 +95,9 @@ def launch(trainer, buf, n, K, outputs=True):
     return dqn_per_fused.train_per(trainer, buf, K, n, indices=indices, td=td), indices, td
 
 
-# capacity, rows added, n, K, double_q, options of make_buffer
+LITERATURE = dict(alpha=0.6, beta=1.0, epsilon=1e-6)
+CORNERS = dict(alpha=1.0, beta=0.0, epsilon=1e-2)
+# capacity, rows added, n, K, double_q, options of make_buffer (per_kwargs: the replay settings), [a set of dqn_cases.PARAMETER_SETS]
 CASES = {
     "root_is_a_leaf": (1, 1, 1, 2, False, {}),
     "two_leaves": (2, 2, 2, 7, True, {}),
@@ -101,19 +112,24 @@ CASES = {
     "large_tree_few_rows": (100_003, 60_000, 31, 7, True, {}),
     "clip_active": (37, 37, 33, 2, False, dict(reward_scale=1e3, obs_scale=400.0)),
     "all_terminal_zero_rewards": (37, 37, 2, 7, False, dict(terminal=True)),
+    "literature_replay_settings": (37, 37, 33, 2, False, dict(per_kwargs=LITERATURE)),
+    "corner_replay_settings_all_moved": (37, 37, 33, 2, True, dict(per_kwargs=CORNERS), "all_moved"),
 }
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_one_launch_equals_k_rounds_of_the_existing_entries(name):
-    capacity, rows, n, K, double_q, options = CASES[name]
+    capacity, rows, n, K, double_q, options = CASES[name][:6]
+    kw = dict(dqn_cases.PARAMETER_SETS[CASES[name][6]] if len(CASES[name]) > 6 else {}, double_q=double_q)
     rng = np.random.default_rng(sum(map(ord, name)))
     theta, target = dqn_cases.random_theta(rng), dqn_cases.random_theta(rng)
     buf = make_buffer(rng, capacity, rows, **options)
     assert buf.size == min(rows, capacity) and buf.pos == rows % capacity
-    ref_buf = clone(buf)
+    ref_buf = clone(buf, options.get("per_kwargs"))
+    for k, v in (options.get("per_kwargs") or {}).items():
+        assert getattr(buf.sum_tree.params, k) == getattr(ref_buf.sum_tree.params, k) == v
     start = buf.sum_tree.tree.clone()
-    fused, steps = make(theta, target, double_q, seed=SEED), make(theta, target, double_q)
+    fused, steps = make_set(theta, target, kw, seed=SEED), make_set(theta, target, kw)
     fused.serial = SERIAL0
     losses, indices, td = launch(fused, buf, n, K)
     want = composition(steps, ref_buf, n, K, SEED, SERIAL0)
@@ -138,13 +154,14 @@ def test_one_launch_equals_k_rounds_of_the_existing_entries(name):
         assert float(np.sqrt(np.sum(g.astype(np.float64) ** 2))) > 10.0
 
 
-@pytest.mark.parametrize("capacity, n, K", [(6, 2, 3), (37, 33, 2), (1000, 256, 2)])
-def test_one_launch_equals_the_composed_numpy_twin(capacity, n, K):
+@pytest.mark.parametrize("capacity, n, K, per_kwargs", [(6, 2, 3, {}), (37, 33, 2, {}), (1000, 256, 2, {}), (37, 33, 2, LITERATURE)],
+                         ids=["6-2-3", "37-33-2", "1000-256-2", "37-33-2-literature"])
+def test_one_launch_equals_the_composed_numpy_twin(capacity, n, K, per_kwargs):
     rng = np.random.default_rng(capacity + n)
     theta, target = dqn_cases.random_theta(rng), dqn_cases.random_theta(rng)
-    buf = make_buffer(rng, capacity, capacity)
+    buf = make_buffer(rng, capacity, capacity, per_kwargs=per_kwargs)
     host = {k: getattr(buf, k).cpu().numpy() for k in FIELDS}
-    twin_tree = per_numpy.SumTree(capacity)
+    twin_tree = per_numpy.SumTree(capacity, **per_kwargs)
     twin_tree.tree[:] = buf.sum_tree.tree.cpu().numpy()
     twin = tw.Twin(theta, target, double_q=capacity == 37)
     fused = make(theta, target, capacity == 37, seed=SEED)
@@ -213,14 +230,18 @@ def test_refusals_enqueue_nothing():
     before, tree_before = tr.state.clone(), buf.sum_tree.tree.clone()
     lib, losses = dqn_per_fused._bind(tr._lib), torch.zeros(4, device=DEV)
 
-    def call(n_entries=40, n=8, K=1, tree=buf.sum_tree.tree.data_ptr()):
-        return lib.mpcgpu_dqn_train_per_dev(0, C.byref(tr.params), C.byref(buf.sum_tree.params), tr.state.data_ptr(), tree,
+    def call(n_entries=40, n=8, K=1, tree=buf.sum_tree.tree.data_ptr(), beta=0.4):
+        pp = buf.sum_tree.params
+        per = type(pp)(pp.capacity, pp.update_max_freq, pp.alpha, beta, pp.epsilon, pp.initial_priority)
+        return lib.mpcgpu_dqn_train_per_dev(0, C.byref(tr.params), C.byref(per), tr.state.data_ptr(), tree,
                                             buf.obs.data_ptr(), buf.next_obs.data_ptr(), buf.actions.data_ptr(), buf.rewards.data_ptr(),
                                             buf.dones.data_ptr(), n_entries, n, K, 1, 0, losses.data_ptr(), None, None,
                                             torch.cuda.current_stream().cuda_stream)
     for kw, text in ((dict(n=0), "1 <= n <= 256"), (dict(n=257), "1 <= n <= 256"), (dict(K=0), "1 <= K <= 65536"),
                      (dict(K=65537), "1 <= K <= 65536"), (dict(n_entries=0), "1 <= n_entries <= capacity"),
-                     (dict(n_entries=65), "1 <= n_entries <= capacity"), (dict(tree=None), "null pointer")):
+                     (dict(n_entries=65), "1 <= n_entries <= capacity"), (dict(tree=None), "null pointer"),
+                     (dict(beta=float("nan")), "0 <= beta < inf"), (dict(beta=-0.4), "0 <= beta < inf"),
+                     (dict(beta=float("inf")), "0 <= beta < inf")):
         assert call(**kw) < 0 and text in lib.mpcgpu_dqn_per_last_error().decode(), kw
     uniform = dqn_train.ReplayBuffer(64, 46, torch.device(DEV))
     b = dqn_cases.random_batch(rng, 40)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from support import per_numpy  # noqa: E402
+from support import per_numpy, pow_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 rl_env = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.rl_env")
@@ -66,7 +66,13 @@ class Pair:
 
 
 def test_hip_replays_the_reference_trace():
-    fx = np.load(os.path.join(GOLDEN, "per_trace.npz"))
+    """the reference's own class at its defaults, at (alpha, beta, epsilon) = (0.6, 1.0, 1e-6) and at (1.0, 0.0, 1e-2) with
+    initial_priority 2.5 (make_per_fixture.py SETTINGS)"""
+    for name in ("per_trace.npz", "per_trace_a06_b10_e1e-6.npz", "per_trace_a10_b00_e1e-2_p25.npz"):
+        hip_replays_the_reference_trace(np.load(os.path.join(GOLDEN, name)))
+
+
+def hip_replays_the_reference_trace(fx):
     p = Pair(int(fx["capacity"]), alpha=float(fx["alpha"]), beta=float(fx["beta"]), epsilon=float(fx["epsilon"]),
              update_max_freq=int(fx["update_max_freq"]), initial_priority=float(fx["initial_priority"]))
     for step, rows in enumerate(fx["rows"]):
@@ -104,6 +110,90 @@ def test_hip_equals_the_twin_at_the_limits(capacity):
     assert per_numpy.check_invariant(p.hip.tree.cpu().numpy())
 
 
+@pytest.mark.parametrize("capacity", [3, 1000])
+def test_hip_equals_the_twin_off_the_default_settings(capacity):
+    """The walk of test_hip_equals_the_twin_at_the_limits at alpha 0.6, beta 1.0, epsilon 1e-6 (the settings of the literature)."""
+    rng = np.random.default_rng(capacity)
+    p = Pair(capacity, alpha=0.6, beta=1.0, epsilon=1e-6, update_max_freq=1000)
+    for n in (1, 4096, 32768, 1, 4096):
+        p.add(n)
+        for rows in (1, 32, 4096):
+            idx = p.sample(rng.random(rows))
+            p.update(idx, (rng.standard_normal(rows) * np.exp(rng.uniform(-3, 2))).astype(np.float32))
+        p.update(np.full(4096, idx[0]), rng.standard_normal(4096).astype(np.float32))     # the highest row wins
+        p.update(np.full(1, idx[-1]), rng.standard_normal(1).astype(np.float32))
+    assert per_numpy.check_invariant(p.hip.tree.cpu().numpy())
+
+
+@pytest.mark.parametrize("alpha, epsilon", pow_cases.SWEEP)
+def test_power_sweep_through_update(alpha, epsilon):
+    """One update rewrites all 4096 leaves of a full tree with pow(|td| + epsilon, alpha), x a full float64: the device's
+    restated pow (csrc/per_pow.hpp) on general (x, y > 0), the whole tree and the state block bitwise against the twin's
+    ``math.pow``.  The census is taken on these inputs: all 128 intervals of the log table in every case."""
+    td = pow_cases.td_errors(per_tree.MAX_ROWS)
+    c = pow_cases.census(*pow_cases.priority_arguments(td, alpha, epsilon))
+    assert len(td) == 4096 and (td == 0).sum() == 1 and (td == 1).sum() == 1 and (td < 0).sum() > 2000
+    assert c["log_intervals"] == list(range(128))
+    assert c["kinds"]["table"] + c["kinds"]["tiny"] >= 4095 and c["kinds"]["x_zero"] == (1 if epsilon == 0.0 else 0)
+    if alpha >= 0.1:
+        assert c["exp_entries"] == list(range(128))
+    else:                                   # y log x stays small: the early return |y log x| < 2^-54 instead (x = 1 + 2^-52)
+        assert c["kinds"]["tiny"] >= 1
+    print(f"alpha {alpha}, epsilon {epsilon}: {c['kinds']}, {len(c['exp_entries'])} exp entries")
+    p = Pair(4096, alpha=alpha, epsilon=epsilon)
+    p.add(4096)
+    p.update(np.arange(4096) + 4095, td)
+    assert np.array_equal(p.twin.leaves, np.array([math.pow(abs(float(t)) + epsilon, alpha) for t in td]))
+
+
+def test_exact_cases_of_the_settings():
+    td = pow_cases.td_errors(per_tree.MAX_ROWS)
+    rng = np.random.default_rng(12)
+    # alpha = 0: y = 0 leaves the restated pow; every written leaf is exactly 1
+    p = Pair(4096, alpha=0.0, epsilon=1e-6)
+    p.add(4096)
+    p.update(np.arange(4096) + 4095, td)
+    assert np.all(p.hip.tree[4095:].cpu().numpy() == 1.0)
+    # epsilon = 0 and td = 0: x = 0; that leaf is exactly 0 and a sample of 4096 never returns it (the others stay positive)
+    p = Pair(4096, alpha=0.6, epsilon=0.0)
+    p.add(4096)
+    p.update(np.arange(4096) + 4095, td)
+    leaves = p.hip.tree[4095:].cpu().numpy()
+    zero = np.flatnonzero(td == 0)
+    assert len(zero) == 1 and leaves[zero[0]] == 0.0 and not np.signbit(leaves[zero[0]]) and np.all(np.delete(leaves, zero) > 0.0)
+    for u in (rng.random(4096), np.zeros(4096), np.full(4096, 1.0 - 2.0 ** -53)):
+        assert 4095 + zero[0] not in p.sample(u).tolist()
+    # beta = 0: -beta = -0.0 leaves the restated pow; every weight is exactly 1
+    p = Pair(1000, beta=0.0)
+    p.add(1000)
+    p.update(np.arange(1000) + 999, td[:1000])
+    p.sample(rng.random(4096))
+    w = p.hip.sample(torch.from_numpy(rng.random(4096)).to(DEV), 1000)[2].cpu().numpy()
+    assert np.all(w == np.float32(1.0))
+    # beta = 1: within one float32 ulp of the twin (Pair.sample's bound)
+    p = Pair(1000, beta=1.0)
+    p.add(1000)
+    p.update(np.arange(1000) + 999, (rng.standard_normal(1000) * 3.0).astype(np.float32))
+    for n in (1, 33, 4096):
+        p.sample(rng.random(n))
+
+
+def test_a_subnormal_argument_goes_through_the_device_library():
+    """epsilon = 1e-310 and td = 0: x is subnormal, outside the restated pow.  DESIGN.md 8.2 reports the device library's pow
+    within one ulp of the C library's; that is the bound here, on this one argument at three exponents.  The tree's sums are
+    compared with sums of the DEVICE's leaves (the twin's leaves are math.pow's and may differ by that ulp)."""
+    for alpha in (0.3, 0.6, 1.0):
+        hip = per_tree.SumTree(5, DEV, alpha=alpha, epsilon=1e-310)
+        hip.add(0, 5, 0)
+        hip.update(torch.tensor([4, 6], device=DEV), torch.tensor([0.0, 0.5], dtype=torch.float32, device=DEV))
+        tree = hip.tree.cpu().numpy()
+        want = math.pow(1e-310, alpha)
+        ulps = abs(int(np.float64(tree[4]).view(np.int64)) - int(np.float64(want).view(np.int64)))
+        print(f"pow(1e-310, {alpha}) on the device {float(tree[4]).hex()}, math.pow {want.hex()}: {ulps} ulp apart")
+        assert ulps <= 1
+        assert tree[6] == math.pow(0.5 + 1e-310, alpha) and per_numpy.check_invariant(tree)
+
+
 def test_update_ignores_indices_that_are_not_leaves_and_sizes_are_checked():
     p = Pair(37)
     p.add(20)
@@ -115,7 +205,18 @@ def test_update_ignores_indices_that_are_not_leaves_and_sizes_are_checked():
         p.hip.sample(torch.zeros(4, dtype=torch.float64, device=DEV), 0)
     with pytest.raises(MpcGpuError, match="pos"):
         p.hip.add(37, 1, 20)
+    # a beta the header excludes (NaN, negative, infinite) is refused by every entry, and nothing is written
+    before = (p.hip.tree.clone(), p.hip.state.clone())
+    idx, u = torch.full((4,), 40, dtype=torch.int64, device=DEV), torch.zeros(4, dtype=torch.float64, device=DEV)
+    for beta in (float("nan"), -0.4, float("inf")):
+        p.hip.params.beta = beta
+        for call in (lambda: p.hip.sample(u, 20), lambda: p.hip.update(idx, torch.ones(4, device=DEV)), lambda: p.hip.add(0, 1, 20),
+                     p.hip.reset, p.hip.stats):
+            with pytest.raises(MpcGpuError, match="invalid mpcgpu_per_params.*0 <= beta < inf"):
+                call()
+    p.hip.params.beta = 0.4
     torch.cuda.synchronize()
+    assert torch.equal(p.hip.tree, before[0]) and torch.equal(p.hip.state[:4], before[1][:4])
 
 
 def test_sample_and_update_replay_from_a_captured_graph():

@@ -503,7 +503,7 @@ int32_t mpcgpu_dqn_train_per_dev(int32_t device, const mpcgpu_dqn_params* dqn, c
                                  uint64_t seed, uint64_t serial0, float* losses, int64_t* indices, float* td, void* stream) {
     using namespace dqngpu;
     if (!valid(dqn)) return fail_per("invalid mpcgpu_dqn_params (lr, max_grad_norm, eps > 0, 0 <= beta < 1, double_q 0 / 1)");
-    if (!pergpu::valid(per)) return fail_per("invalid mpcgpu_per_params (capacity 1..2^30, update_max_freq >= 1, alpha, epsilon >= 0, initial_priority > 0)");
+    if (!pergpu::valid(per)) return fail_per("invalid mpcgpu_per_params (capacity 1..2^30, update_max_freq >= 1, alpha, epsilon >= 0, 0 <= beta < inf, initial_priority > 0)");
     if (n < 1 || n > MPCGPU_DQN_MAX_ROWS) return fail_per("1 <= n <= 256");
     if (K < 1 || K > MPCGPU_DQN_MAX_STEPS) return fail_per("1 <= K <= 65536");
     if (n_entries < 1 || n_entries > per->capacity) return fail_per("1 <= n_entries <= capacity");

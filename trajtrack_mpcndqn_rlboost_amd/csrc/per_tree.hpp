@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 
@@ -24,7 +25,7 @@ __host__ __device__ inline int depth_of(int64_t i) { return 63 - __builtin_clzll
 
 inline bool valid(const mpcgpu_per_params* p) {
     return p && p->capacity >= 1 && p->capacity <= ((int64_t)1 << 30) && p->update_max_freq >= 1 && p->alpha >= 0.0 &&
-           p->epsilon >= 0.0 && p->initial_priority > 0.0;
+           p->beta >= 0.0 && p->beta <= DBL_MAX && p->epsilon >= 0.0 && p->initial_priority > 0.0;      // a NaN fails every comparison
 }
 
 // the point row i of n descends with: u in [0, 1) of the way through stratum i of [0, total)

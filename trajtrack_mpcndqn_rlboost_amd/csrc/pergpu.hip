@@ -203,7 +203,7 @@ int fail(const char* what, hipError_t e = hipSuccess) {
 }
 
 int begin(int32_t device, const mpcgpu_per_params* p) {
-    if (!valid(p)) return fail("invalid mpcgpu_per_params (capacity 1..2^30, update_max_freq >= 1, alpha, epsilon >= 0, initial_priority > 0)");
+    if (!valid(p)) return fail("invalid mpcgpu_per_params (capacity 1..2^30, update_max_freq >= 1, alpha, epsilon >= 0, 0 <= beta < inf, initial_priority > 0)");
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return fail("hipSetDevice", e);
     return 0;
