@@ -505,4 +505,4 @@ def test_device_tick_follows_the_host_tick_at_forty_steps():
     assert dev._chosen.shape == (B, 40, 3) and dev._rl_ref.shape == (B, 20, 2)
     print(f"\n[tracker limits] device tick at N_hor = 40: robot-ticks compared on a common trajectory: {n_compared} of {3 * B}")
     assert n_compared > 0                                        # the two loops did run side by side
-    host.tracker.solver.close(); dev.dtracker.solver.close()
+    host.tracker.solver.close(); dev.tracker.solver.close()

@@ -196,7 +196,7 @@ def test_batched_hybrid_tracks_forty_rows_with_the_twenty_row_proposal():
 
     B = 3
     run = hybrid.BatchedHybrid.__new__(hybrid.BatchedHybrid)
-    run._torch, run.config, run.mode, run.B = torch, cfg, 2, B
+    run._torch, run.config, run.mode, run.B, run.profile = torch, cfg, 2, B, False
     run.env, run.q_net, run.tracker = StubEnv(B), StubNet(), StubTracker(B)
     run.tracker.states[:] = [[1.0, 1.0, 0.0], [1.0, 5.0, 0.0], [1.0, 9.0, 0.0]]
     run.maps = [dict(obstacles=[])] * B

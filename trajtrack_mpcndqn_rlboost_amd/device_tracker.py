@@ -73,6 +73,12 @@ class DeviceTracker:
     def set_mode(self, mode: str):
         self.base_speed, self.tuning = work_mode(self.config, mode)
 
+    @property
+    def ref_trajs(self):
+        """The global reference trajectories, a list of arrays like ``BatchedTracker.ref_trajs``: the host copies that
+        ``initialization`` keeps."""
+        return list(self._h_ref)
+
     # -- per-robot set-up (host, like BatchedTracker's) ----------------------------------------------------------------
     def initialization(self, i: int, init_state, goal_state, ref_path_list: Sequence[Sequence[float]], mode: str = "work"):
         base_speed, _ = work_mode(self.config, mode)

@@ -12,10 +12,13 @@ Pieces (each mirrors one reference item):
   Q-network action, 20-step RL reference (``dqn.rl_reference``), constant-velocity obstacle predictions
   (``feeders``), reference switch, one batched MPC solve (``BatchedTracker`` -> ``libmpcgpu.so``).
   ``decision_mode``: 0 pure DQN, 1 pure MPC, 2 hybrid -- as in ``main.py:96-98``.
+* :class:`HybridLoop`     -- what that loop and ``device_hybrid.DeviceHybrid`` (the same tick on the device) share: the scene
+  set-up, ``reset``, the end-of-tick accounting and ``run``.
 """
 from __future__ import annotations
 
 import math
+import time
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -235,14 +238,16 @@ class BatchedHintSwitcher:
 
 
 # ---- the batched decision loop ----------------------------------------------------------------------------------------
-class BatchedHybrid:
-    """B robots, each in its own copy of a scene.  ``scenes[i]``: dict with ``boundary``, ``static`` (polygons),
-    ``dynamic`` (``rl_env.periodic_obstacle`` arguments), ``start`` (x, y, theta, v, w), ``goal`` (x, y), ``path``.
+class HybridLoop:
+    """What the decision loop does wherever its tick runs: B robots, each in its own copy of a scene.  ``scenes[i]``: dict
+    with ``boundary``, ``static`` (polygons), ``dynamic`` (``rl_env.periodic_obstacle`` arguments), ``start`` (x, y, theta, v,
+    w), ``goal`` (x, y), ``path``.
 
-    One tick = one environment kernel launch + one Q-network forward + one batched MPC solve."""
+    A subclass gives ``_build`` (``self.tracker`` and whatever else it keeps from construction on; the scene tables below exist
+    by then), ``_clear`` (its own per-episode state, called by ``reset``) and ``tick``."""
 
     def __init__(self, config: MpcConfig, scenes: Sequence[Dict], q_net: QNetwork, decision_mode: int = 2,
-                 device: int = 0, inflate_margin: float = 0.8, switcher=(10, 2, 10), tracker: Optional[BatchedTracker] = None):
+                 device: int = 0, inflate_margin: float = 0.8, switcher=(10, 2, 10)):
         import torch
         if decision_mode not in (0, 1, 2):
             raise ValueError("decision_mode: 0 pure DQN, 1 pure MPC, 2 hybrid")
@@ -253,9 +258,7 @@ class BatchedHybrid:
                      for s in scenes]
         self.env = rl_env.BatchedRaysEnv(self.maps, device=device, time_step=0.2)   # gym.make default (environment.py:53)
         self.q_net = q_net.to(self.env.device)
-        self.tracker = tracker if tracker is not None else BatchedTracker(config, self.B, device=device)
         self.inflated = [[inflate_polygon(poly, inflate_margin) for poly in s["static"]] for s in scenes]
-        self.switcher = BatchedHintSwitcher(self.B, *switcher)
         n_dyn = max(len(s["dynamic"]) for s in scenes)
         self._n_static = np.array([len(s["static"]) for s in scenes])
         self._n_dynamic = np.array([len(s["dynamic"]) for s in scenes])
@@ -268,17 +271,18 @@ class BatchedHybrid:
                 self._polygons[b, :len(polys)] = pad_polygons(polys, vmax)
             self._poly_valid[b, :len(polys)] = True
             self._poly_valid[b, self._n_static.max():self._n_static.max() + self._n_dynamic[b]] = True
+        self.profile, self.phase_seconds, self._last_mark = False, {}, 0.0    # the per-tick breakdown of _mark
+        self._build(device, switcher)
         self.reset()
 
     def reset(self):
-        cfg = self.config
         self.obs = self.env.reset()
         for i, s in enumerate(self.scenes):
             start = np.asarray(s["start"], dtype=float)
             self.tracker.initialization(i, start[:3], np.array([s["goal"][0], s["goal"][1], 0.0]), s["path"])
             self.tracker.update_static_constraints(i, self.inflated[i])
-        self.switcher.reset()
-        self.last_dyn = None
+        self._clear()
+        self.last_dyn = None                              # the obstacle positions of the tick before
         self.done = np.zeros(self.B, dtype=bool)
         self.success = np.zeros(self.B, dtype=bool)
         self.collided = np.zeros(self.B, dtype=bool)
@@ -286,6 +290,77 @@ class BatchedHybrid:
         self.switch_on = np.zeros(self.B, dtype=bool)
         self.switch_ticks = np.zeros(self.B, dtype=int)   # ticks on which the MPC tracked the DQN's proposal
         self.t = 0
+
+    def _account(self, collided, success, ended, switch_on, states) -> Dict[str, np.ndarray]:
+        """The end of a tick, on host arrays [B].  ``collided``, ``success`` and ``ended`` (the environment terminated the robot
+        or the tracker's own termination test fired) count for the robots that were live when the tick began; ``switch_on``
+        (the robot tracked the DQN's proposal on this tick) comes masked with them already.  Returns the tick's result."""
+        live = ~self.done
+        self.collided |= live & collided
+        self.success |= live & success
+        self.done |= live & ended
+        self.switch_on = switch_on
+        self.switch_ticks += switch_on
+        self.steps += live
+        self.t += 1
+        return dict(done=self.done.copy(), success=self.success.copy(), collided=self.collided.copy(),
+                    switch_on=self.switch_on.copy(), states=states)
+
+    def _flat(self, obs):
+        return self._torch.cat([obs["external"], obs["internal"]], dim=1)
+
+    def _mark(self, name: str) -> None:
+        """Per-tick breakdown (``self.phase_seconds``; enabled by ``self.profile = True``): wall time between marks with the
+        device drained at every mark, so that a phase is charged with the kernels it launched."""
+        if not self.profile:
+            return
+        self._torch.cuda.synchronize()
+        now = time.perf_counter()
+        if name != "start":
+            self.phase_seconds[name] = self.phase_seconds.get(name, 0.0) + now - self._last_mark
+        self._last_mark = now
+
+    def run(self, max_steps: int = MAX_RUN_STEP, record: bool = False) -> Dict[str, np.ndarray]:
+        """Run until every robot is done (or ``max_steps``).  ``record=True`` also returns what the reference's
+        ``Metrics.add_trial_result`` consumes per robot (``main_evaluation.py:255-266``): tick times [ms], (v, w) history,
+        traversed positions and the global reference trajectory (see ``metrics.Metrics.add_batch``)."""
+        out = None
+        tick_ms = [[] for _ in range(self.B)]
+        actions = [[(float(s["start"][3]), float(s["start"][4]))] for s in self.scenes]
+        positions = [[(float(s["start"][0]), float(s["start"][1]))] * 2 for s in self.scenes]   # update_status appends twice at reset
+        for _ in range(max_steps):
+            live = ~self.done
+            t0 = time.perf_counter()
+            out = self.tick()
+            dt = 1e3 * (time.perf_counter() - t0)
+            if record:
+                st = self.env.agent_state.cpu().numpy()
+                for b in np.nonzero(live)[0]:
+                    tick_ms[b].append(dt)
+                    actions[b].append((float(st[b, 3]), float(st[b, 4])))
+                    positions[b].append((float(st[b, 0]), float(st[b, 1])))
+            if out["done"].all():
+                break
+        res = dict(out, steps=self.steps.copy(), switch_ticks=self.switch_ticks.copy(),
+                   progress=self.env.path_progress.cpu().numpy())
+        if record:
+            res["record"] = dict(tick_ms=tick_ms, success=self.success.copy(), actions=actions, positions=positions,
+                                 ref_traj=[np.array(t) for t in self.tracker.ref_trajs])
+        return res
+
+
+class BatchedHybrid(HybridLoop):
+    """The loop with the tick's logic on the host, in numpy: the reference the device loop is tested against, and the only loop
+    that runs decision mode 0.
+
+    One tick = one environment kernel launch + one Q-network forward + one batched MPC solve."""
+
+    def _build(self, device, switcher):
+        self.tracker = BatchedTracker(self.config, self.B, device=device)
+        self.switcher = BatchedHintSwitcher(self.B, *switcher)
+
+    def _clear(self):
+        self.switcher.reset()
 
     def dynamic_positions(self) -> np.ndarray:
         """[B, Kmax, 2]: current key-frame positions of every environment's dynamic obstacles (main.py:127); rows
@@ -296,23 +371,6 @@ class BatchedHybrid:
             for j, ob in enumerate(m["obstacles"][self._n_static[b]:]):
                 out[b, j] = rl_env.keyframe_pose(ob, clock[b])[:2]
         return out
-
-    def _flat(self, obs):
-        return self._torch.cat([obs["external"], obs["internal"]], dim=1)
-
-    def _mark(self, name: str) -> None:
-        """Per-tick breakdown (``self.phase_seconds``; enabled by ``self.profile = True``): wall time between marks with the
-        device drained at every mark, so that a phase is charged with the kernels it launched."""
-        if not getattr(self, "profile", False):
-            return
-        import time
-        self._torch.cuda.synchronize()
-        now = time.perf_counter()
-        if not hasattr(self, "phase_seconds"):
-            self.phase_seconds = {}
-        if name != "start":
-            self.phase_seconds[name] = self.phase_seconds.get(name, 0.0) + now - self._last_mark
-        self._last_mark = now
 
     def tick(self) -> Dict[str, np.ndarray]:
         torch, cfg, env, trk = self._torch, self.config, self.env, self.tracker
@@ -326,6 +384,7 @@ class BatchedHybrid:
             preds = np.where(has, constant_velocity_prediction(self.last_dyn, dyn_now, steps=cfg.N_hor), 0.0)
         self.last_dyn = dyn_now
         live = ~self.done
+        switch_on = np.zeros(self.B, dtype=bool)             # modes 0 and 1: nobody tracks the proposal
         self._mark("obstacle predictions (host)")
 
         if self.mode == 0:                                   # pure DQN: main.py:139-152
@@ -361,53 +420,18 @@ class BatchedHybrid:
                     self._polygons[:, s0:s0 + kmax, 4:] = rects[:, :, 3:4]
                 on = self.switcher.switch(trk.states[:, :2], original, self._polygons, self._poly_valid, live,
                                           proposal_rows=rl_ref.shape[1])
-                self.switch_on = on & live
-                self.switch_ticks += self.switch_on
-                chosen = tracked_reference(original, rl_ref, self.switch_on)   # N_hor rows: the proposal has 20
+                switch_on = on & live
+                chosen = tracked_reference(original, rl_ref, switch_on)        # N_hor rows: the proposal has 20
                 self._mark("RL reference + switch (host)")
             if kmax:
                 trk.set_dynamic_constraints(preds)
             trk.active &= live
             trk.step(refs=chosen)
             self._mark("parameter assembly + batched MPC solve")
-            # get_action returns None once the tracker's own termination test fires (interface_mpc.py:83-85)
-            self.done |= live & ~trk.active
         term = term.cpu().numpy().astype(bool)
         flags = env.flags.cpu().numpy()
-        self.success |= live & flags[:, 2]
-        self.collided |= live & (flags[:, 0] | flags[:, 1])
-        self.done |= live & term
-        self.steps += live
-        self.t += 1
+        # get_action returns None once the tracker's own termination test fires (interface_mpc.py:83-85); mode 0 never steps
+        # the tracker, whose robots all stay active
+        out = self._account(flags[:, 0] | flags[:, 1], flags[:, 2], term | ~trk.active, switch_on, trk.states.copy())
         self._mark("bookkeeping (host)")
-        return dict(done=self.done.copy(), success=self.success.copy(), collided=self.collided.copy(),
-                    switch_on=self.switch_on.copy(), states=trk.states.copy())
-
-    def run(self, max_steps: int = MAX_RUN_STEP, record: bool = False) -> Dict[str, np.ndarray]:
-        """Run until every robot is done (or ``max_steps``).  ``record=True`` also returns what the reference's
-        ``Metrics.add_trial_result`` consumes per robot (``main_evaluation.py:255-266``): tick times [ms], (v, w) history,
-        traversed positions and the global reference trajectory (see ``metrics.Metrics.add_batch``)."""
-        import time
-        out = None
-        tick_ms = [[] for _ in range(self.B)]
-        actions = [[(float(s["start"][3]), float(s["start"][4]))] for s in self.scenes]
-        positions = [[(float(s["start"][0]), float(s["start"][1]))] * 2 for s in self.scenes]   # update_status appends twice at reset
-        for _ in range(max_steps):
-            live = ~self.done
-            t0 = time.perf_counter()
-            out = self.tick()
-            dt = 1e3 * (time.perf_counter() - t0)
-            if record:
-                st = self.env.agent_state.cpu().numpy()
-                for b in np.nonzero(live)[0]:
-                    tick_ms[b].append(dt)
-                    actions[b].append((float(st[b, 3]), float(st[b, 4])))
-                    positions[b].append((float(st[b, 0]), float(st[b, 1])))
-            if out["done"].all():
-                break
-        res = dict(out, steps=self.steps.copy(), switch_ticks=self.switch_ticks.copy(),
-                   progress=self.env.path_progress.cpu().numpy())
-        if record:
-            res["record"] = dict(tick_ms=tick_ms, success=self.success.copy(), actions=actions, positions=positions,
-                                 ref_traj=[np.array(t) for t in self.tracker.ref_trajs])
-        return res
+        return out
