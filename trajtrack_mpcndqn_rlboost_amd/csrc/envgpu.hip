@@ -11,8 +11,11 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
+#include "../../include/mpcgpu_collect.h"
 #include "../../include/mpcgpu_map.h"
+#include "dqn_act.hpp"
 #include "envgpu_internal.hpp"
 
 namespace envgpu {
@@ -101,11 +104,33 @@ __constant__ double DIRS[16] = {0.0, 0.38268343236508978178, 0.70710678118654757
                                 0.0, -0.38268343236508978178, -0.70710678118654757274, -0.92387953251128673848,
                                 -1.0, -0.92387953251128673848, -0.70710678118654757274, -0.38268343236508978178};
 
+// COLLECT (include/mpcgpu_collect.h): what the step kernel gets on top of its own arguments, and nothing without it
+struct CollectK {
+    const float* theta;
+    float* buf_obs; float* buf_next_obs; int64_t* buf_actions; float* buf_rewards; float* buf_dones;
+    double* ep_return;
+    int32_t* actions; uint8_t* done; uint8_t* success; double* episode_return;   // [T][B], each may be NULL
+    mpcgpu_collect_params p;
+};
+struct NoCollect {};
+__device__ __forceinline__ int collect_steps(const CollectK& co) { return co.p.T; }
+__device__ __forceinline__ int collect_steps(const NoCollect&) { return 1; }
+__device__ __forceinline__ dqnact::ActLds& collect_lds() {   // LDS of the instantiations that call it only
+    __shared__ dqnact::ActLds lds;
+    return lds;
+}
+
 // FRESH (include/mpcgpu_map.h): rec_all is a [2][B][rec] table, row b steps on table which[b], and an episode that ends while
 // spare_ready[b] is set starts its next episode on the other table.  Everything FRESH adds sits under `if constexpr`.
-template <bool FRESH>
+// COLLECT (include/mpcgpu_collect.h): the body below runs co.p.T times; before each step the wavefront chooses its action from
+// the observation the previous step left in global memory, after it the transition goes into the ring.  Every trip reads the
+// state and writes it back exactly as a launch of its own does, so T trips are T launches; everything COLLECT adds sits under
+// `if constexpr`, and without it the loop is `do { } while (false)`.
+template <bool FRESH, bool COLLECT = false>
 __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double* __restrict__ rec_all, double* state_all,
-                                                        const int32_t* __restrict__ action, EnvOut out, int B, EnvFresh fr) {
+                                                        const int32_t* __restrict__ action, EnvOut out, int B, EnvFresh fr,
+                                                        std::conditional_t<COLLECT, CollectK, NoCollect> co) {
+    static_assert(!(FRESH && COLLECT), "collection on the two-record table is not built");
     float* const obs_int = out.obs_int;
     float* const obs_ext = out.obs_ext;
     double* const reward = out.reward;
@@ -121,15 +146,41 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
     const mpcgpu_env_params& P = k.p;
     int n_path = (int)rec[0], n_obst = (int)rec[1], n_edge = (int)rec[2];   // (not const: FRESH re-reads them with the record)
     double gx = rec[3], gy = rec[4];
+    int t = 0, chosen = 0;
+    double ep_ret = 0.0;
+    if constexpr (COLLECT) {
+        dqnact::stage_theta(collect_lds(), co.theta, lane, WAVE);
+        ep_ret = co.ep_return[b];
+    }
+    do {
+    if constexpr (COLLECT) {
+        // ---- the action (include/mpcgpu_collect.h): the flat observation, external then internal, into LDS.  From the second trip
+        //      on it is what this workgroup wrote: the fence and the barrier in front of the ring stores below cover these reads too
+        dqnact::ActLds& L = collect_lds();
+        __syncthreads();   // the ring stores of the previous trip have read L.x
+        if (lane < MPCGPU_ENV_EXTERNAL_OBS) L.x[lane] = obs_ext[(size_t)b * MPCGPU_ENV_EXTERNAL_OBS + lane];
+        else if (lane < dqnact::OBS) L.x[lane] = obs_int[(size_t)b * MPCGPU_ENV_INTERNAL_OBS + lane - MPCGPU_ENV_EXTERNAL_OBS];
+        __syncthreads();
+        chosen = dqnact::act(L, lane, co.p.eps[t], co.p.seed, co.p.serial0 + (uint64_t)t, (uint64_t)b);
+    }
     double x = st[0], y = st[1], th = st[2], v = st[3], w = st[4], clock = st[5];
     double last_prog = st[6], steps = st[25];
     int flags = (int)st[7];
     bool act = action != nullptr;
-    const double ts = P.time_step;
+    double ts = P.time_step;
+    if constexpr (COLLECT) {
+        act = true;
+        // The time step must not be a loop invariant: the compiler would hoist products such as ts * P.angacc_max out of the loop over
+        // t, and a product formed up there is no longer fused into the addition it feeds (-ffp-contract=fast fuses within a block),
+        // so a trip would round differently from a launch of its own.  Behind the empty barrier every trip computes them anew.
+        asm volatile("" : "+s"(ts));
+    }
 
     // ---- obstacles' clock and the robot (environment.py:199-203, agent.py:97-139); every lane keeps the same copy
     if (act) {
-        const int a = action[b];
+        int a;
+        if constexpr (COLLECT) a = chosen;
+        else a = action[b];
         clock += ts;
         const int row = a / 3, col = a % 3;
         if (row == 0) v += ts * P.acc_max;
@@ -418,8 +469,7 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
     return pass == 0 && out.max_steps > 0 && act && (collided || reached || timeout);
     };  // run_pass
 
-    if (!run_pass(0, cth0, sth0)) return;
-
+    if (run_pass(0, cth0, sth0)) {
     // ---- the episode ended: keep its last observation, go back to the start state (environment.py:166-186) and
     //      observe once more.  The observation memory (st[8..23]) is not cleared -- the reference's component keeps it.
     __threadfence();
@@ -446,6 +496,60 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
     clock = 0.0; flags = 0; steps = 0.0; last_prog = 0.0; act = false;
     sincos(th, &sth0, &cth0);
     run_pass(1, cth0, sth0);
+    }
+    if constexpr (COLLECT) {
+        // ---- the transition (dqn_train.ReplayBuffer.add as DqnLearner.learn calls it) and the episode return, read back from
+        //      what the step wrote: the same words the host-driven round reads.  Writers and readers are lanes of this one
+        //      workgroup, so a workgroup-scope fence orders them; an agent-scope __threadfence() here, once per step in every
+        //      wavefront, writes back and invalidates L2 lines across the whole device and cost most of the launch
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __syncthreads();
+        const dqnact::ActLds& L = collect_lds();
+        const bool term = terminated[b] != 0, ended = term || out.truncated[b] != 0;
+        const double r = reward[b];
+        const size_t slot = (size_t)t * B + b;
+        const size_t row = (size_t)(((uint64_t)co.p.pos0 + slot) % (uint64_t)co.p.capacity);
+        if (lane < dqnact::OBS) {
+            const bool ext = lane < MPCGPU_ENV_EXTERNAL_OBS;
+            const float* src = ext ? (ended ? out.term_ext : obs_ext) + (size_t)b * MPCGPU_ENV_EXTERNAL_OBS + lane
+                                   : (ended ? out.term_int : obs_int) + (size_t)b * MPCGPU_ENV_INTERNAL_OBS + lane - MPCGPU_ENV_EXTERNAL_OBS;
+            co.buf_obs[row * dqnact::OBS + lane] = L.x[lane];
+            co.buf_next_obs[row * dqnact::OBS + lane] = *src;
+        }
+        ep_ret = ep_ret + r;
+        if (lane == 0) {
+            co.buf_actions[row] = chosen;
+            co.buf_rewards[row] = (float)r;
+            co.buf_dones[row] = term ? 1.0f : 0.0f;
+            if (co.actions) co.actions[slot] = chosen;
+            if (co.done) co.done[slot] = ended ? 1 : 0;
+            if (co.success) co.success[slot] = ((int)st[26] & 4) ? 1 : 0;
+            if (ended && co.episode_return) co.episode_return[slot] = ep_ret;
+        }
+        if (ended) ep_ret = 0.0;
+    }
+    } while (COLLECT && ++t < collect_steps(co));
+    if constexpr (COLLECT) {
+        if (lane == 0) co.ep_return[b] = ep_ret;
+    }
+}
+
+// the action rule alone (mpcgpu_collect_act_dev): one wavefront per workgroup, the rows dealt out over the grid
+__global__ __launch_bounds__(WAVE) void collect_act_kernel(const float* __restrict__ theta, const float* __restrict__ obs_ext,
+                                                          const float* __restrict__ obs_int, int B, double eps, uint64_t seed,
+                                                          uint64_t serial, int32_t* actions, float* q) {
+    __shared__ dqnact::ActLds L;
+    const int lane = threadIdx.x;
+    dqnact::stage_theta(L, theta, lane, WAVE);
+    for (int b = blockIdx.x; b < B; b += gridDim.x) {
+        __syncthreads();
+        if (lane < MPCGPU_ENV_EXTERNAL_OBS) L.x[lane] = obs_ext[(size_t)b * MPCGPU_ENV_EXTERNAL_OBS + lane];
+        else if (lane < dqnact::OBS) L.x[lane] = obs_int[(size_t)b * MPCGPU_ENV_INTERNAL_OBS + lane - MPCGPU_ENV_EXTERNAL_OBS];
+        __syncthreads();
+        const int a = dqnact::act(L, lane, eps, seed, serial, (uint64_t)b);
+        if (lane == 0) actions[b] = a;
+        if (q && lane < dqnact::ACT) q[(size_t)b * dqnact::ACT + lane] = L.q[lane];
+    }
 }
 
 thread_local std::string g_err;
@@ -457,26 +561,39 @@ int fail(const char* what, hipError_t e) {
     return -1;
 }
 
+// what launch_step refuses in the params, or NULL; fills k
+const char* params_error(const mpcgpu_env_params* params, EnvK& k) {
+    if (!params || !layout(*params, k)) return "invalid mpcgpu_env_params (P 2..64, M 0..31, K 1..4, E >= 1)";
+    if (params->num_segments != NSEG || params->corner_samples != NCORNER)
+        return "only num_segments = 8 and corner_samples = 3 are built (rays_reward1.py:18-20)";
+    return nullptr;
+}
+
 int launch_step(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records, double* state,
                 const int32_t* action, EnvOut out, bool need_ext, void* stream, const EnvFresh* fresh) {
     EnvK k;
-    if (!params || !layout(*params, k)) return fail("invalid mpcgpu_env_params (P 2..64, M 0..31, K 1..4, E >= 1)");
-    if (params->num_segments != NSEG || params->corner_samples != NCORNER)
-        return fail("only num_segments = 8 and corner_samples = 3 are built (rays_reward1.py:18-20)");
+    if (const char* bad = params_error(params, k)) return fail(bad);
     if (B < 0 || !records || !state || !out.obs_int || (need_ext && !out.obs_ext)) return fail("null pointer / negative batch");
     if (B == 0) return 0;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return fail("hipSetDevice", e);
     if (fresh)
         hipLaunchKernelGGL(env_step_kernel<true>, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state, action, out,
-                           (int)B, *fresh);
+                           (int)B, *fresh, NoCollect{});
     else
         hipLaunchKernelGGL(env_step_kernel<false>, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state, action, out,
-                           (int)B, EnvFresh{});
+                           (int)B, EnvFresh{}, NoCollect{});
     e = hipGetLastError();
     if (e != hipSuccess) return fail("env_step_kernel launch", e);
     return 0;
 }
+
+thread_local std::string g_collect_err;
+int collect_fail(const char* what, hipError_t e = hipSuccess) {
+    g_collect_err = e != hipSuccess ? std::string(what) + ": " + hipGetErrorString(e) : std::string(what);
+    return -1;
+}
+bool eps_ok(double eps) { return eps >= 0.0 && eps <= 1.0; }   // false for NaN
 
 }  // namespace envgpu
 
@@ -524,5 +641,66 @@ int32_t mpcgpu_env_step_fresh_dev(int32_t device, const mpcgpu_env_params* param
     const envgpu::EnvFresh fresh{which, spare_ready, loaded, stale};
     return envgpu::launch_step(device, params, B, records2, state, action, out, true, stream, &fresh);
 }
+
+}  // extern "C"
+
+// include/mpcgpu_collect.h
+extern "C" {
+
+int32_t mpcgpu_collect_act_dev(int32_t device, const float* theta, const float* obs_external, const float* obs_internal,
+                               int32_t B, double eps, uint64_t seed, uint64_t serial, int32_t* actions, float* q, void* stream) {
+    using namespace envgpu;
+    if (!theta || !obs_external || !obs_internal || !actions) return collect_fail("null pointer (theta / obs_external / obs_internal / actions)");
+    if (B < 0) return collect_fail("negative batch");
+    if (!eps_ok(eps)) return collect_fail("eps must lie in [0, 1]");
+    if (B == 0) return 0;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return collect_fail("hipSetDevice", e);
+    hipLaunchKernelGGL(collect_act_kernel, dim3(B < 1024 ? B : 1024), dim3(WAVE), 0, (hipStream_t)stream, theta, obs_external,
+                       obs_internal, (int)B, eps, seed, serial, actions, q);
+    e = hipGetLastError();
+    if (e != hipSuccess) return collect_fail("collect_act_kernel launch", e);
+    return 0;
+}
+
+int32_t mpcgpu_collect_rays_dev(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records, double* state,
+                                float* obs_internal, float* obs_external, double* reward, uint8_t* terminated,
+                                uint8_t* truncated, float* terminal_obs_internal, float* terminal_obs_external,
+                                int32_t max_episode_steps, const float* theta, const mpcgpu_collect_params* collect,
+                                float* buf_obs, float* buf_next_obs, int64_t* buf_actions, float* buf_rewards, float* buf_dones,
+                                double* ep_return, int32_t* actions, uint8_t* done, uint8_t* success, double* episode_return,
+                                void* stream) {
+    using namespace envgpu;
+    EnvK k;
+    if (const char* bad = params_error(params, k)) return collect_fail(bad);
+    if (!records || !state || !obs_internal || !obs_external || !reward || !terminated || !truncated || !terminal_obs_internal ||
+        !terminal_obs_external)
+        return collect_fail("null pointer (an environment tensor)");
+    if (!theta || !collect || !buf_obs || !buf_next_obs || !buf_actions || !buf_rewards || !buf_dones || !ep_return)
+        return collect_fail("null pointer (theta / collect / ring / ep_return)");
+    if (B < 0) return collect_fail("negative batch");
+    if (max_episode_steps <= 0) return collect_fail("max_episode_steps must be positive");
+    if (collect->T < 1 || collect->T > MPCGPU_COLLECT_MAX_STEPS) return collect_fail("1 <= T <= 64 (MPCGPU_COLLECT_MAX_STEPS)");
+    if (collect->capacity < 1 || collect->pos0 < 0 || collect->pos0 >= collect->capacity)
+        return collect_fail("capacity >= 1 and 0 <= pos0 < capacity");
+    if ((int64_t)collect->T * B > collect->capacity)
+        return collect_fail("T * B must not exceed capacity: the rows of one launch would overwrite each other");
+    for (int t = 0; t < collect->T; ++t)
+        if (!eps_ok(collect->eps[t])) return collect_fail("every eps[t], t < T, must lie in [0, 1]");
+    if (B == 0) return 0;
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return collect_fail("hipSetDevice", e);
+    const EnvOut out{obs_internal, obs_external, reward, terminated, truncated, terminal_obs_internal, terminal_obs_external,
+                     max_episode_steps, nullptr};
+    const CollectK co{theta, buf_obs, buf_next_obs, buf_actions, buf_rewards, buf_dones, ep_return, actions, done, success,
+                      episode_return, *collect};
+    hipLaunchKernelGGL((env_step_kernel<false, true>), dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state,
+                       (const int32_t*)nullptr, out, (int)B, EnvFresh{}, co);
+    e = hipGetLastError();
+    if (e != hipSuccess) return collect_fail("env_step_kernel launch", e);
+    return 0;
+}
+
+const char* mpcgpu_collect_last_error(void) { return envgpu::g_collect_err.c_str(); }
 
 }  // extern "C"

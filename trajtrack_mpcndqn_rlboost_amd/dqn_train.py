@@ -385,7 +385,8 @@ class DqnLearner:
                  target_update_interval: int = 10_000, exploration_fraction: float = 0.2,
                  exploration_initial_eps: float = 1.0, exploration_final_eps: float = 0.05, seed: int = 0,
                  use_graph: bool = False, track_episodes: bool = True, per: bool = False,
-                 per_kwargs: Optional[Dict] = None, fused: bool = False, per_in_kernel: bool = False):
+                 per_kwargs: Optional[Dict] = None, fused: bool = False, per_in_kernel: bool = False,
+                 collect_in_kernel: bool = False, collect_launch_steps: Optional[int] = None):
         """``per=True``: prioritized experience replay (the reference's ``'per': True``): the buffer keeps a sum tree of
         priorities (``per_kwargs``: alpha, beta, epsilon, update_max_freq, initial_priority), minibatches are drawn by
         priority, the loss is weighted by the importance weights and the drawn rows are re-prioritized with their TD errors
@@ -399,7 +400,14 @@ class DqnLearner:
         ``per_in_kernel=True`` (needs ``fused=True`` and ``per=True``, one rank): the round is ONE launch with prioritized
         replay too -- the kernel samples the tree, updates and re-prioritises step after step
         (:meth:`dqn_fused.FusedDqnTrainer.train_per`), its uniforms from the same counter stream.  The
-        checkpoint has the same keys either way and moves between the two settings."""
+        checkpoint has the same keys either way and moves between the two settings.
+
+        ``collect_in_kernel=True`` (ray environment on one record table, any ray trainer): the ``train_freq`` steps a round of
+        ``learn`` collects -- act, auto-reset step, buffer rows, episode returns -- are ONE launch of the step kernel
+        (:func:`collect.collect_rays`), or launches of ``collect_launch_steps`` steps each (at most 64; the
+        default is the whole round).  Exploration then draws from the counter stream ``(collect_seed, collect_serial)``, both
+        part of ``state_dict``, instead of the torch generator, so the actions are not those of the host-driven loop; the
+        target network is synchronised once behind a round whose steps reach the interval."""
         if per_in_kernel and not (fused and per):
             raise ValueError("per_in_kernel=True needs fused=True and per=True: it is the prioritized form of the fused K-step launch")
         self.env, self.device = env, env.device
@@ -448,6 +456,17 @@ class DqnLearner:
         # state of the collection loop between two learn() calls (a run can be checkpointed and resumed in the middle)
         self._obs, self._ep_return, self.n_updates = None, None, 0
         self._last_loss = torch.zeros((), device=self.device)
+        self.collect_in_kernel = bool(collect_in_kernel)
+        if self.collect_in_kernel:
+            from . import collect, dqn_fused
+            collect.check_env(env)
+            dqn_fused.check_shape(self.trainer.q_net)
+            if collect_launch_steps is not None and int(collect_launch_steps) < 1:
+                raise ValueError("collect_launch_steps must be at least 1")
+            self.collect_launch_steps = collect.MAX_STEPS if collect_launch_steps is None else min(int(collect_launch_steps), collect.MAX_STEPS)
+            # not the trainer's fused_seed (seed + rank): minibatch rows and exploration must not share a stream
+            self.collect_seed, self.collect_serial = ((seed + rank) ^ 0x436F6C6C65637421) % 2 ** 64, 0
+            self._collect_out = None
 
     def _prepare(self, obs):
         """The network's input: the flat vector for rays, the dictionary itself for images."""
@@ -474,6 +493,10 @@ class DqnLearner:
                  obs=_map_obs(torch.clone, self._obs), ep_return=_map_obs(torch.clone, self._ep_return))
         if self.fused:
             d["fused_seed"], d["fused_serial"] = tr.seed, tr.serial
+        if self.collect_in_kernel:
+            d["collect_seed"], d["collect_serial"] = self.collect_seed, self.collect_serial
+            if self._obs is not None:     # the loop stands at the observation the environment holds
+                d["obs"] = self._prepare(self.env._obs())
         if include_buffer:
             d["buffer"] = self.buffer.state_dict()
         if hasattr(self.env, "state_dict"):
@@ -487,6 +510,8 @@ class DqnLearner:
         tr.num_updates, tr.num_target_syncs = d["num_updates"], d["num_target_syncs"]
         if self.fused:
             tr.seed, tr.serial = d["fused_seed"], d["fused_serial"]
+        if self.collect_in_kernel and "collect_seed" in d:
+            self.collect_seed, self.collect_serial = d["collect_seed"], d["collect_serial"]
         self.num_timesteps, self.n_calls, self.n_updates = d["num_timesteps"], d["n_calls"], d["n_updates"]
         self.gen.set_state(d["generator"].cpu())   # a generator state is a host ByteTensor, also for a device generator
         self.episode_returns, self.episode_successes = list(d["episode_returns"]), list(d["episode_successes"])
@@ -508,6 +533,46 @@ class DqnLearner:
         """The policy alone (the reference's final_model / best_model): the Q-network's weights."""
         torch.save(self.trainer.q_net.state_dict(), path)
 
+    def _collect_round(self, total_timesteps: int, ep_return: torch.Tensor) -> int:
+        """One round's steps inside the step kernel (``collect_in_kernel``): the steps the host-driven loop would make, with its
+        epsilons, in launches of ``collect_launch_steps``; then the episode statistics from the [T, B] outputs in the order
+        (t, then b ascending), and one target sync if any of the round's steps is due one.  Returns the transitions collected."""
+        from . import collect
+        B = self.env.B
+        n = min(self.train_freq, -(-(total_timesteps - self.num_timesteps) // B))
+        state = getattr(self.trainer, "state", None)      # the fused state block begins with theta
+        theta = state if isinstance(state, torch.Tensor) else torch.cat(
+            [p.detach().reshape(-1) for p in self.trainer.q_net.parameters()]).to(device=self.device, dtype=torch.float32).contiguous()
+        if self._collect_out is None:
+            self._collect_out = {name: torch.zeros(self.collect_launch_steps, B, dtype=dtype, device=self.device)
+                                 for name, dtype in collect.OUTPUTS}
+        every, sync, made = max(self.target_update_interval // B, 1), False, 0
+        while made < n:
+            T = min(n - made, self.collect_launch_steps)
+            eps = [exploration_rate(self.num_timesteps + t * B, total_timesteps, *self.eps) for t in range(T)]
+            out = {name: x[:T] for name, x in self._collect_out.items()}
+            collect.collect_rays(self.env, theta, self.buffer, eps, self.collect_seed, self.collect_serial, ep_return, out)
+            done, success = out["done"].bool(), out["success"].bool()
+            if self.track_episodes:
+                if bool(done.any()):
+                    self.episode_returns += out["episode_return"][done].tolist()
+                    self.episode_successes += success[done].tolist()
+            else:
+                # the two counts are sums of integers, exact in float64 in any order: one reduction per launch; the returns are
+                # summed per step, as the host-driven loop sums them, so the sum keeps its bits whatever the launch size
+                self.ep_count += done.sum()
+                self.ep_success_sum += (success & done).sum()
+                for t in range(T):
+                    self.ep_return_sum += torch.where(done[t], out["episode_return"][t], torch.zeros_like(ep_return)).sum()
+            sync = sync or any((self.n_calls + t + 1) % every == 0 for t in range(T))
+            self.collect_serial += T
+            self.num_timesteps += T * B
+            self.n_calls += T
+            made += T
+        if sync:
+            self.trainer.sync_target()
+        return n * B
+
     def learn(self, total_timesteps: int, callback: Optional[Callable[["DqnLearner"], None]] = None,
               stop_at: Optional[int] = None) -> Dict[str, float]:
         """Collect and learn until ``total_timesteps`` (the horizon of the exploration schedule) -- or until ``stop_at``, a
@@ -519,8 +584,8 @@ class DqnLearner:
         obs, ep_return, n_updates, last_loss = self._obs, self._ep_return, self.n_updates, self._last_loss
         end = total_timesteps if stop_at is None else min(stop_at, total_timesteps)
         while self.num_timesteps < end:
-            collected = 0
-            for _ in range(self.train_freq):
+            collected = self._collect_round(total_timesteps, ep_return) if self.collect_in_kernel else 0
+            for _ in range(0 if self.collect_in_kernel else self.train_freq):
                 eps = exploration_rate(self.num_timesteps, total_timesteps, *self.eps)
                 actions = self.act(obs, eps)
                 nxt, reward, terminated, truncated, info = env.step(actions, auto_reset=True)
