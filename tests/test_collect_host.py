@@ -15,12 +15,11 @@ import pytest
 import torch
 
 from support import collect_numpy as cn, dqn_cases, dqn_numpy as tw
-from trajtrack_mpcndqn_rlboost_amd import collect, dqn, dqn_fused, dqn_per_fused, dqn_train, rl_env
+from trajtrack_mpcndqn_rlboost_amd import collect, dqn, dqn_fused, dqn_train, rl_env
 
 solver_mod = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.solver")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-ARGUMENTS = {"mpcgpu_collect_act_dev": 11, "mpcgpu_collect_rays_dev": 26, "mpcgpu_collect_last_error": 0}
 
 
 def declared(header):
@@ -29,31 +28,6 @@ def declared(header):
 
 
 # ---- binding ---------------------------------------------------------------------------------------------------------------
-def test_export_tuple_is_the_key_tuple_of_the_table():
-    assert isinstance(collect.COLLECT_EXPORTS, tuple) and collect.COLLECT_EXPORTS == tuple(collect._COLLECT_TABLE)
-    assert set(collect.COLLECT_EXPORTS) == set(ARGUMENTS)
-    for name, (restype, argtypes) in collect._COLLECT_TABLE.items():
-        assert len(argtypes) == ARGUMENTS[name], name
-        assert restype is (C.c_char_p if name.endswith("_last_error") else C.c_int32), name
-    others = set(rl_env.ENV_EXPORTS) | set(dqn_fused.DQN_EXPORTS) | set(dqn_per_fused.DQN_PER_EXPORTS)
-    assert not set(collect.COLLECT_EXPORTS) & others
-
-
-def test_a_library_that_lacks_an_export_is_refused_by_name():
-    exports = collect.COLLECT_EXPORTS
-    for gone in exports:
-        stand_in = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in exports if e != gone})
-        with pytest.raises(solver_mod.MpcGpuError) as err:
-            collect._bind(stand_in)
-        text = str(err.value)
-        assert gone in text and "csrc/envgpu.hip" in text and "rebuild" in text and "no fallback" in text
-        assert not any(hasattr(fn, "argtypes") for fn in vars(stand_in).values())
-    other = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in rl_env.ENV_EXPORTS})
-    rl_env._bind(other)
-    with pytest.raises(solver_mod.MpcGpuError, match="mpcgpu_collect_act_dev"):      # the tag is this table's own
-        collect._bind(other)
-
-
 def test_the_built_library_and_the_header_have_exactly_these_exports():
     path = solver_mod.library_path()
     assert os.path.exists(path), f"{path} missing -- run __graft_entry__.build()"

@@ -1,7 +1,6 @@
 """The fused DQN update without a GPU: the binding table of ``dqn_fused``, the numpy twin of csrc/dqngpu.hip
 (tests/support/dqn_numpy.py) against float64 evaluations of the same step, its sampler against Python integers, the refusals
 of ``DqnLearner(fused=True)`` and ``FusedDqnTrainer``, and Adam's ``state_dict`` between the two trainers."""
-import ctypes as C
 import importlib
 import types
 
@@ -14,32 +13,9 @@ from trajtrack_mpcndqn_rlboost_amd import dqn, dqn_fused, dqn_train, map_stream
 
 solver_mod = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.solver")
 F = np.float32
-ARGUMENTS = {"mpcgpu_dqn_state_floats": 0, "mpcgpu_dqn_grad_dev": 14, "mpcgpu_dqn_apply_dev": 6, "mpcgpu_dqn_step_dev": 14,
-             "mpcgpu_dqn_train_dev": 15, "mpcgpu_dqn_last_error": 0}
 
 
 # ---- binding ---------------------------------------------------------------------------------------------------------------
-def test_export_tuple_is_the_key_tuple_of_the_table():
-    assert isinstance(dqn_fused.DQN_EXPORTS, tuple) and dqn_fused.DQN_EXPORTS == tuple(dqn_fused._DQN_TABLE)
-    assert set(dqn_fused.DQN_EXPORTS) == set(ARGUMENTS)
-    for name, (restype, argtypes) in dqn_fused._DQN_TABLE.items():
-        assert len(argtypes) == ARGUMENTS[name], name
-        assert restype is (C.c_char_p if name.endswith("_last_error") else C.c_int32), name
-
-
-def test_a_library_that_lacks_an_export_is_refused_by_name():
-    exports = dqn_fused.DQN_EXPORTS
-    for gone in exports:
-        stand_in = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in exports if e != gone})
-        with pytest.raises(solver_mod.MpcGpuError) as err:
-            dqn_fused._bind(stand_in)
-        text = str(err.value)
-        assert gone in text and "csrc/dqngpu.hip" in text and "rebuild" in text and "no fallback" in text
-        assert not any(hasattr(fn, "argtypes") for fn in vars(stand_in).values())      # refused before anything was set
-    whole = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in exports})
-    assert dqn_fused._bind(whole) is whole and len(whole.mpcgpu_dqn_train_dev.argtypes) == 15
-
-
 def test_the_built_library_has_the_exports_and_the_state_layout():
     lib = dqn_fused._bind(solver_mod.load_library())
     assert lib.mpcgpu_dqn_state_floats() == tw.STATE_FLOATS == 4 * tw.NP + 4 and dqn_fused.STATE_T == tw.STATE_T

@@ -19,7 +19,6 @@ from trajtrack_mpcndqn_rlboost_amd import dqn_fused, dqn_per_fused, dqn_train, p
 solver_mod = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.solver")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-ARGUMENTS = {"mpcgpu_dqn_train_per_dev": 19, "mpcgpu_dqn_per_last_error": 0}
 
 
 def declared(header):
@@ -28,33 +27,6 @@ def declared(header):
 
 
 # ---- binding ---------------------------------------------------------------------------------------------------------------
-def test_export_tuple_is_the_key_tuple_of_the_table():
-    assert isinstance(dqn_per_fused.DQN_PER_EXPORTS, tuple) and dqn_per_fused.DQN_PER_EXPORTS == tuple(dqn_per_fused._DQN_PER_TABLE)
-    assert set(dqn_per_fused.DQN_PER_EXPORTS) == set(ARGUMENTS)
-    for name, (restype, argtypes) in dqn_per_fused._DQN_PER_TABLE.items():
-        assert len(argtypes) == ARGUMENTS[name], name
-        assert restype is (C.c_char_p if name.endswith("_last_error") else C.c_int32), name
-    assert not set(dqn_per_fused.DQN_PER_EXPORTS) & (set(dqn_fused.DQN_EXPORTS) | set(per_tree.PER_EXPORTS))
-
-
-def test_a_library_that_lacks_an_export_is_refused_by_name():
-    exports = dqn_per_fused.DQN_PER_EXPORTS
-    for gone in exports:
-        stand_in = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in exports if e != gone})
-        with pytest.raises(solver_mod.MpcGpuError) as err:
-            dqn_per_fused._bind(stand_in)
-        text = str(err.value)
-        assert gone in text and "csrc/dqngpu.hip" in text and "rebuild" in text and "no fallback" in text
-        assert not any(hasattr(fn, "argtypes") for fn in vars(stand_in).values())      # refused before anything was set
-    whole = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in exports})
-    assert dqn_per_fused._bind(whole) is whole and len(whole.mpcgpu_dqn_train_per_dev.argtypes) == 19
-    # the tag is this table's own: a handle bound for the other two tables is still asked for these exports
-    other = types.SimpleNamespace(**{e: types.SimpleNamespace() for e in dqn_fused.DQN_EXPORTS + per_tree.PER_EXPORTS})
-    dqn_fused._bind(other); per_tree._bind(other)
-    with pytest.raises(solver_mod.MpcGpuError, match="mpcgpu_dqn_train_per_dev"):
-        dqn_per_fused._bind(other)
-
-
 def test_the_built_library_and_the_header_have_exactly_these_exports():
     path = solver_mod.library_path()
     assert os.path.exists(path), f"{path} missing -- run __graft_entry__.build()"

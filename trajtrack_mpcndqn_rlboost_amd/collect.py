@@ -14,10 +14,11 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from .dqn import N_ACTIONS, OBS_DIM
+from .dqn_fused import N_PARAMS
+from .dqn_train import check_ray_buffer
 from .rl_env import N_EXTERNAL, N_INTERNAL, _CParams
 from .solver import MpcGpuError, bind_exports, load_library
 
-N_PARAMS = 1177
 MAX_STEPS = 64
 OUTPUTS = (("actions", torch.int32), ("done", torch.uint8), ("success", torch.uint8), ("episode_return", torch.float64))
 
@@ -109,13 +110,7 @@ def collect_rays(env, theta: torch.Tensor, buffer, eps: Sequence[float], seed: i
     T, B = len(eps), env.B
     device = env.device
     theta = _theta(theta, device)
-    for name, dtype in (("obs", torch.float32), ("next_obs", torch.float32), ("actions", torch.int64),
-                        ("rewards", torch.float32), ("dones", torch.float32)):
-        x = getattr(buffer, name, None)
-        if x is None or x.dtype != dtype or not x.is_contiguous() or x.device != device or x.shape[0] != buffer.capacity:
-            raise ValueError(f"buffer.{name} must be {buffer.capacity} rows of contiguous {dtype} on {device}")
-    if buffer.obs.shape[1:] != (OBS_DIM,) or buffer.next_obs.shape != buffer.obs.shape:
-        raise ValueError(f"the buffer holds observations of shape {tuple(buffer.obs.shape[1:])}, not ({OBS_DIM},)")
+    check_ray_buffer(buffer, device)
     if ep_return.dtype != torch.float64 or ep_return.shape != (B,) or not ep_return.is_contiguous() or ep_return.device != device:
         raise ValueError(f"ep_return must be {B} contiguous float64 values on {device}")
     ptr = {}

@@ -10,26 +10,19 @@
 
 #include <cstdint>
 
-#include "../../include/mpcgpu_dqn.h"
+#include "counter_stream.hpp"
+#include "dqn_layout.hpp"
 
 namespace dqnact {
 
-constexpr int OBS = MPCGPU_DQN_OBS, HID = MPCGPU_DQN_HIDDEN, ACT = MPCGPU_DQN_ACTIONS;
-constexpr int OFF_W0 = 0, OFF_B0 = 736, OFF_W1 = 752, OFF_B1 = 1008, OFF_W2 = 1024, OFF_B2 = 1168;
+using namespace dqn_layout;      // OBS, HID, ACT and the offsets OFF_W0 .. OFF_B2 into theta
 static_assert(OFF_B2 + ACT == MPCGPU_DQN_PARAMS, "parameter layout of mpcgpu_dqn.h");
-constexpr uint64_t G = 0x9E3779B97F4A7C15ull;
 
 // theta with its rows padded to an odd stride (lane j reads row j: 16 lanes, 16 banks), the observation, the activations
 struct ActLds {
     float w0[HID][OBS + 1], b0[HID], w1[HID][HID + 1], b1[HID], w2[ACT][HID + 1], b2[ACT];
     float x[OBS], h1[HID], h2[HID], q[ACT];
 };
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // the SplitMix64 finaliser (include/mpcgpu_map.h)
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ float mul_then_add(float acc, float w, float x) {   // two rounded operations, never one
     float p = w * x;
@@ -73,10 +66,9 @@ __device__ inline int act(ActLds& L, int lane, double eps, uint64_t seed, uint64
         const float qa = L.q[a];
         if (qa > best) { best = qa; greedy = a; }
     }
-    const uint64_t key = mix64(seed + G * serial);
-    const uint64_t bits_e = mix64(key + G * (2 * b + 1)), bits_a = mix64(key + G * (2 * b + 2));
-    const double u = (double)(bits_e >> 11) * 0x1.0p-53;
-    return u < eps ? (int)__umul64hi(bits_a, 9ull) : greedy;
+    const uint64_t key = counter_stream::key_of(seed, serial);      // row b owns draws 2 b (explore?) and 2 b + 1 (which action)
+    const uint64_t bits_e = COUNTER_STREAM_DRAW(key, 2 * b + 1), bits_a = COUNTER_STREAM_DRAW(key, 2 * b + 2);
+    return counter_stream::unit(bits_e) < eps ? (int)__umul64hi(bits_a, 9ull) : greedy;
 }
 
 }  // namespace dqnact

@@ -39,14 +39,14 @@
 
 #include "../../include/mpcgpu_dqn.h"
 #include "../../include/mpcgpu_dqn_per.h"
+#include "counter_stream.hpp"
+#include "dqn_layout.hpp"
 #include "per_tree.hpp"
 
 namespace dqngpu {
 
 constexpr int NT = MPCGPU_DQN_MAX_ROWS;     // threads = rows at most
-constexpr int OBS = MPCGPU_DQN_OBS, HID = MPCGPU_DQN_HIDDEN, ACT = MPCGPU_DQN_ACTIONS, NP = MPCGPU_DQN_PARAMS;
-constexpr int OFF_W0 = 0, OFF_B0 = OFF_W0 + HID * OBS, OFF_W1 = OFF_B0 + HID, OFF_B1 = OFF_W1 + HID * HID,
-              OFF_W2 = OFF_B1 + HID, OFF_B2 = OFF_W2 + ACT * HID;
+using namespace dqn_layout;                 // OBS, HID, ACT, NP and the offsets OFF_W0 .. OFF_B2 into a parameter vector
 static_assert(OFF_B2 + ACT == NP, "parameter layout");
 // the same vector in LDS: W0's rows padded to 48 words, so that every matrix row is 16-byte aligned
 constexpr int OBS_PAD = 48, PAD = HID * (OBS_PAD - OBS);
@@ -59,7 +59,6 @@ constexpr int R_X = 0, R_H1 = R_X + OBS, R_H2 = R_H1 + HID, R_DZ0 = R_H2 + HID, 
 static_assert(RS == 121, "an odd record stride");
 constexpr int ST_THETA = 0, ST_TARGET = NP, ST_M = 2 * NP, ST_V = 3 * NP;
 static_assert(4 * NP == MPCGPU_DQN_STATE_T, "state layout");
-constexpr uint64_t GOLDEN = 0x9E3779B97F4A7C15ull;
 
 enum : int { DO_GRAD = 1, DO_APPLY = 2, DO_SAMPLE = 4 };
 
@@ -83,12 +82,6 @@ struct Args {
 };
 
 __host__ __device__ constexpr int lds_pos(int p) { return p < OFF_B0 ? (p / OBS) * OBS_PAD + p % OBS : p + PAD; }
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // SplitMix64 finaliser, as csrc/mapgpu.hip
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 using pergpu::pow_as_libm;
 
@@ -202,6 +195,8 @@ __global__ void __launch_bounds__(NT) dqn_kernel(const Args a, const std::condit
     __syncthreads();
 
     for (int s = 0; s < a.steps; ++s) {
+        // the step's key of the counter stream: row t takes draw t, its uniform in phase S or its buffer row in phase A
+        const uint64_t key = counter_stream::key_of(a.seed, a.serial0 + (uint64_t)s);
         int64_t leaf = 0;            // PER: this row's tree index, its weight, its delta and whether it is the highest row of its leaf
         float drawn_w = 1.0f, delta = 0.0f;
         bool wins = false;
@@ -212,8 +207,7 @@ __global__ void __launch_bounds__(NT) dqn_kernel(const Args a, const std::condit
             const double total = tr.tree[0];
             double w = -INFINITY;
             if (t < n) {
-                const uint64_t key = mix64(a.seed + GOLDEN * (a.serial0 + (uint64_t)s));
-                const double u = (double)(mix64(key + GOLDEN * (uint64_t)(t + 1)) >> 11) * 0x1.0p-53;
+                const double u = counter_stream::unit(COUNTER_STREAM_DRAW(key, (uint64_t)(t + 1)));
                 leaf = pergpu::descend(tr.tree, 2 * tr.C - 1, pergpu::stratum_point(total, n, t, u));
                 w = pergpu::raw_weight(tr.n_entries, tr.tree[leaf], total, tr.beta);
                 if (tr.indices) tr.indices[(int64_t)s * n + t] = leaf;
@@ -241,10 +235,7 @@ __global__ void __launch_bounds__(NT) dqn_kernel(const Args a, const std::condit
             if (t < n) {
                 int64_t row = t;
                 if constexpr (PER) row = leaf - (tr.C - 1);
-                if (sample) {
-                    const uint64_t key = mix64(a.seed + GOLDEN * (a.serial0 + (uint64_t)s));
-                    row = (int64_t)__umul64hi(mix64(key + GOLDEN * (uint64_t)(t + 1)), (uint64_t)a.size);
-                }
+                if (sample) row = (int64_t)__umul64hi(COUNTER_STREAM_DRAW(key, (uint64_t)(t + 1)), (uint64_t)a.size);
                 float x[OBS], h1[HID], h2[HID], q[ACT], scan[ACT];
                 load_row(a.next_obs, row, x);
                 network(tt, x, h1, h2, q);

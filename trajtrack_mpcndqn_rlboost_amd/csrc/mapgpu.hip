@@ -17,6 +17,7 @@
 #include <string>
 
 #include "../../include/mpcgpu_map.h"
+#include "counter_stream.hpp"
 #include "envgpu_internal.hpp"
 
 namespace mapgpu {
@@ -32,15 +33,9 @@ static_assert(SPEC == O_PERIODIC + MPCGPU_MAP_MAX_PERIODIC * PERIODIC_STRIDE, "s
 
 constexpr int N_STATIC = 3, N_PERIODIC = 7;   // generate_map_dynamic: ten obstacles, the first three are boxes
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // SplitMix64 finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// draw k of the map with key `key`: lo + (hi - lo) * u_k, as CounterUniform.uniform
+// draw k of the map with key `key`: lo + (hi - lo) * u_k, as CounterUniform.uniform (two rounded operations: MAP_FLAGS)
 __device__ __forceinline__ double uniform(uint64_t key, int k, double lo, double hi) {
-    const uint64_t bits = mix64(key + 0x9E3779B97F4A7C15ull * (uint64_t)(k + 1));
-    const double u = (double)(bits >> 11) * 0x1p-53;
+    const double u = counter_stream::unit(COUNTER_STREAM_DRAW(key, (uint64_t)(k + 1)));
     return lo + (hi - lo) * u;
 }
 
@@ -51,7 +46,7 @@ __global__ __launch_bounds__(WAVE) void map_draw_kernel(uint64_t seed, double* _
     if (b >= B || spare_ready[b] != 0) return;          // uniform: the whole workgroup leaves
     const int n = attempt[b];
     const uint64_t serial = (uint64_t)b + (uint64_t)B * (uint64_t)n;
-    const uint64_t key = mix64(seed + 0x9E3779B97F4A7C15ull * serial);
+    const uint64_t key = counter_stream::key_of(seed, serial);
     for (int i = lane; i < SPEC; i += WAVE) spec[i] = 0.0;
     __syncthreads();
     const double two_pi = 2.0 * 3.141592653589793;

@@ -15,8 +15,9 @@ from typing import Dict, Optional
 import torch
 import torch.distributed as dist
 
+from . import dqn_per_fused
 from .dqn import N_ACTIONS, OBS_DIM, QNetwork
-from .dqn_train import DqnTrainerBase
+from .dqn_train import DqnTrainerBase, check_ray_buffer
 from .solver import MpcGpuError, bind_exports, load_library
 
 N_PARAMS = 1177
@@ -211,40 +212,42 @@ class FusedDqnTrainer(DqnTrainerBase):
         self._count_updates()
         return self._loss[0]
 
-    def train(self, buffer, k: int, batch_size: int) -> torch.Tensor:
-        """``k`` gradient steps on minibatches of ``batch_size`` rows drawn uniformly from ``buffer`` (a
-        ``dqn_train.ReplayBuffer``) by the kernel itself, 65 536 steps per launch: step s draws from the counter stream
-        ``(seed, serial + s)``, and ``serial`` moves on by ``k``.  Returns the ``k`` losses (device).  The target network is
-        not synchronised inside (``target_update_interval`` does not apply): the learner syncs on environment steps."""
+    def theta(self) -> torch.Tensor:
+        return self.state           # the state block begins with theta: no copy
+
+    def launch_steps(self, k: int, launch, name: str = "train") -> torch.Tensor:
+        """The K-step launch loop of :meth:`train` and :meth:`train_per`: ``k`` steps in launches of at most 65 536.
+        ``launch(part, done, losses)`` enqueues steps ``done .. done + part - 1`` on the stream ``(seed, serial)`` and raises on a
+        refusal; ``serial`` moves on and the updates are counted.  Returns the ``k`` losses (device)."""
         if self._collective:
-            raise MpcGpuError("train() is the one-rank path; several ranks update step by step around the all-reduce")
+            raise MpcGpuError(f"{name}() is the one-rank path; several ranks update step by step around the all-reduce")
         if k < 1:
             raise ValueError(f"k = {k}: at least one step")
-        for name, dtype in (("obs", torch.float32), ("next_obs", torch.float32), ("actions", torch.int64),
-                            ("rewards", torch.float32), ("dones", torch.float32)):
-            x = getattr(buffer, name)
-            if x.dtype != dtype or not x.is_contiguous() or x.device != self.device:
-                raise ValueError(f"buffer.{name} must be contiguous {dtype} on {self.device}")
-        if buffer.obs.shape[1:] != (OBS_DIM,):
-            raise ValueError(f"the buffer holds observations of shape {tuple(buffer.obs.shape[1:])}, not ({OBS_DIM},)")
         losses = torch.empty(k, dtype=torch.float32, device=self.device)
         done = 0
         while done < k:
             part = min(k - done, MAX_STEPS)
-            self._check(self._lib.mpcgpu_dqn_train_dev(
-                self.device_index, C.byref(self.params), self.state.data_ptr(), buffer.obs.data_ptr(), buffer.next_obs.data_ptr(),
-                buffer.actions.data_ptr(), buffer.rewards.data_ptr(), buffer.dones.data_ptr(), int(buffer.size), int(batch_size),
-                part, self.seed % 2 ** 64, self.serial % 2 ** 64, losses[done:].data_ptr(), self._stream()))
+            launch(part, done, losses[done:])
             self.serial += part
             self._count_updates(part, sync=False)
             done += part
         return losses
 
+    def train(self, buffer, k: int, batch_size: int) -> torch.Tensor:
+        """``k`` gradient steps on minibatches of ``batch_size`` rows drawn uniformly from ``buffer`` (a
+        ``dqn_train.ReplayBuffer``) by the kernel itself, 65 536 steps per launch: step s draws from the counter stream
+        ``(seed, serial + s)``, and ``serial`` moves on by ``k``.  Returns the ``k`` losses (device).  The target network is
+        not synchronised inside (``target_update_interval`` does not apply): the learner syncs on environment steps."""
+        check_ray_buffer(buffer, self.device)
+        return self.launch_steps(k, lambda part, done, losses: self._check(self._lib.mpcgpu_dqn_train_dev(
+            self.device_index, C.byref(self.params), self.state.data_ptr(), buffer.obs.data_ptr(), buffer.next_obs.data_ptr(),
+            buffer.actions.data_ptr(), buffer.rewards.data_ptr(), buffer.dones.data_ptr(), int(buffer.size), int(batch_size),
+            part, self.seed % 2 ** 64, self.serial % 2 ** 64, losses.data_ptr(), self._stream())))
+
     def train_per(self, buffer, k: int, batch_size: int) -> torch.Tensor:
         """:meth:`train` on a PRIORITIZED buffer: sample from its sum tree, weighted step, priorities written back, ``k`` times
         in one launch (:func:`dqn_per_fused.train_per`)."""
-        from .dqn_per_fused import train_per
-        return train_per(self, buffer, k, batch_size)
+        return dqn_per_fused.train_per(self, buffer, k, batch_size)
 
     def sync_target(self) -> None:
         """Hard target update: a copy of 1 177 floats inside the state block."""
@@ -265,3 +268,4 @@ class FusedDqnTrainer(DqnTrainerBase):
             self.state[2 * N_PARAMS:3 * N_PARAMS] = m.to(self.device)
             self.state[3 * N_PARAMS:4 * N_PARAMS] = v.to(self.device)
             self._t.fill_(t)
+

@@ -12,15 +12,15 @@ import ctypes as C
 
 import torch
 
-from .dqn import OBS_DIM
-from .dqn_fused import MAX_STEPS, _CDqnParams
+from .dqn_train import check_ray_buffer
 from .per_tree import _CPerParams
-from .solver import MpcGpuError, bind_exports
+from .solver import MpcGpuError, bind_exports, load_library
 
 _VP, _I32, _I64, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
 # export -> (restype, argtypes); include/mpcgpu_dqn_per.h
 _DQN_PER_TABLE = {
-    "mpcgpu_dqn_train_per_dev": (_I32, [_I32, C.POINTER(_CDqnParams), C.POINTER(_CPerParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+    # the second argument is an MpcGpuDqnParams*: the struct is dqn_fused's (which imports this module), passed by reference
+    "mpcgpu_dqn_train_per_dev": (_I32, [_I32, _VP, C.POINTER(_CPerParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                         _I64, _I32, _I32, _U64, _U64, _VP, _VP, _VP, _VP]),
     "mpcgpu_dqn_per_last_error": (C.c_char_p, []),
 }
@@ -32,53 +32,33 @@ def _bind(lib):
 
 
 def check_buffer(trainer, buffer) -> None:
-    """What the kernel assumes of a prioritized ray buffer on the trainer's device; raises before anything is enqueued."""
-    tree = getattr(buffer, "sum_tree", None)
-    if tree is None:
+    """What the kernel assumes of a prioritized ray buffer on the trainer's device (``dqn_train.check_ray_buffer``, and that
+    there is a tree at all); raises before anything is enqueued."""
+    if getattr(buffer, "sum_tree", None) is None:
         raise ValueError("train_per() needs a prioritized buffer (ReplayBuffer(..., per_kwargs={...})); a uniform one goes to train()")
-    for name, dtype in (("obs", torch.float32), ("next_obs", torch.float32), ("actions", torch.int64),
-                        ("rewards", torch.float32), ("dones", torch.float32)):
-        x = getattr(buffer, name)
-        if x.dtype != dtype or not x.is_contiguous() or x.device != trainer.device:
-            raise ValueError(f"buffer.{name} must be contiguous {dtype} on {trainer.device}")
-        if x.shape[0] != tree.capacity:
-            raise ValueError(f"buffer.{name} holds {x.shape[0]} rows, the tree's capacity is {tree.capacity}")
-    if buffer.obs.shape[1:] != (OBS_DIM,):
-        raise ValueError(f"the buffer holds observations of shape {tuple(buffer.obs.shape[1:])}, not ({OBS_DIM},)")
-    t = tree.tree
-    if t.dtype != torch.float64 or not t.is_contiguous() or t.device != trainer.device or t.numel() != 2 * tree.capacity - 1:
-        raise ValueError(f"the sum tree must be {2 * tree.capacity - 1} contiguous float64 values on {trainer.device}")
+    check_ray_buffer(buffer, trainer.device)
 
 
 def train_per(trainer, buffer, k: int, batch_size: int, indices: torch.Tensor = None, td: torch.Tensor = None) -> torch.Tensor:
-    """``k`` gradient steps of ``trainer`` on minibatches of ``batch_size`` rows drawn by priority from ``buffer`` by the kernel
-    itself, 65 536 steps per launch; the contract of ``FusedDqnTrainer.train``: step s draws its uniforms from the counter
-    stream ``(seed, serial + s)``, ``serial`` moves on by ``k``, the target network is not synchronised inside.  Returns the
-    ``k`` losses (device).  ``indices`` (int64 ``[k, batch_size]``) and ``td`` (float32 ``[k, batch_size]``), when given, take
-    every step's tree indices and TD errors."""
-    if trainer.collective:
-        raise MpcGpuError("train_per() is the one-rank path; several ranks update step by step around the all-reduce")
-    if k < 1:
-        raise ValueError(f"k = {k}: at least one step")
+    """``k`` gradient steps of ``trainer`` (a :class:`dqn_fused.FusedDqnTrainer`) on minibatches of ``batch_size`` rows drawn by
+    priority from ``buffer`` by the kernel itself, through the trainer's launch loop and so with the contract of its ``train``:
+    step s draws its uniforms from the counter stream ``(seed, serial + s)``, ``serial`` moves on by ``k``, the target network is
+    not synchronised inside.  Returns the ``k`` losses (device).  ``indices`` (int64 ``[k, batch_size]``) and ``td`` (float32
+    ``[k, batch_size]``), when given, take every step's tree indices and TD errors."""
     check_buffer(trainer, buffer)
     n = int(batch_size)
     for name, x, dtype in (("indices", indices, torch.int64), ("td", td, torch.float32)):
         if x is not None and (x.dtype != dtype or not x.is_contiguous() or x.device != trainer.device or x.numel() != k * max(n, 0)):
             raise ValueError(f"{name} must be {k} x {n} contiguous {dtype} values on {trainer.device}")
-    lib, tree = _bind(trainer._lib), buffer.sum_tree
-    losses = torch.empty(k, dtype=torch.float32, device=trainer.device)
-    done = 0
-    while done < k:
-        part = min(k - done, MAX_STEPS)
+    lib, tree = _bind(load_library()), buffer.sum_tree
+
+    def launch(part, done, losses):
         rc = lib.mpcgpu_dqn_train_per_dev(
             trainer.device_index, C.byref(trainer.params), C.byref(tree.params), trainer.state.data_ptr(), tree.tree.data_ptr(),
             buffer.obs.data_ptr(), buffer.next_obs.data_ptr(), buffer.actions.data_ptr(), buffer.rewards.data_ptr(),
-            buffer.dones.data_ptr(), int(buffer.size), n, part, trainer.seed % 2 ** 64, trainer.serial % 2 ** 64,
-            losses[done:].data_ptr(), None if indices is None else indices.view(-1)[done * n:].data_ptr(),
-            None if td is None else td.view(-1)[done * n:].data_ptr(), trainer._stream())
+            buffer.dones.data_ptr(), int(buffer.size), n, part, trainer.seed % 2 ** 64, trainer.serial % 2 ** 64, losses.data_ptr(),
+            None if indices is None else indices.view(-1)[done * n:].data_ptr(),
+            None if td is None else td.view(-1)[done * n:].data_ptr(), torch.cuda.current_stream(trainer.device).cuda_stream)
         if rc != 0:
             raise MpcGpuError(lib.mpcgpu_dqn_per_last_error().decode())
-        trainer.serial += part
-        trainer._count_updates(part, sync=False)
-        done += part
-    return losses
+    return trainer.launch_steps(k, launch, "train_per")

@@ -17,14 +17,14 @@ import torch.distributed as dist
 from torch import nn
 from torch.nn import functional as F
 
-from .dqn import ImageQNetwork, QNetwork
+from .dqn import OBS_DIM, ImageQNetwork, QNetwork
 from .per_tree import SumTree
 
 
 class DqnTrainerBase:
     """What :class:`DqnTrainer` and :class:`dqn_fused.FusedDqnTrainer` share: the process group (``world``, ``collective``) and
     the update / target-sync counters.  The rest of what :class:`DqnLearner` uses -- ``q_net``, ``q_net_target``, ``optimizer``,
-    ``update``, ``last_td_error``, ``sync_target``, ``load_optimizer_state`` -- is each class's own."""
+    ``update``, ``last_td_error``, ``sync_target``, ``load_optimizer_state``, ``theta`` -- is each class's own."""
 
     def __init__(self, target_update_interval: int, force_collective: bool = False):
         """``force_collective``: all-reduce the gradient (and run what is built around that) in a process group of ONE rank
@@ -43,6 +43,11 @@ class DqnTrainerBase:
         self.num_updates += n
         if sync and self.target_update_interval and self.num_updates % self.target_update_interval == 0:
             self.sync_target()
+
+    def theta(self) -> torch.Tensor:
+        """The online parameters of a ray Q-network as the kernels read them (``collect.collect_rays``): at least 1 177
+        contiguous float32 values on the device, ``QNetwork.parameters()`` in order at the front."""
+        raise NotImplementedError
 
 
 class DqnTrainer(DqnTrainerBase):
@@ -233,6 +238,9 @@ class DqnTrainer(DqnTrainerBase):
                     else:
                         st[k].copy_(torch.as_tensor(src[k]).to(device=st[k].device, dtype=st[k].dtype))
 
+    def theta(self) -> torch.Tensor:
+        return torch.cat([p.detach().reshape(-1) for p in self._params]).to(dtype=torch.float32).contiguous()
+
     def sync_target(self) -> None:
         """Hard target update (SB3 ``polyak_update`` with tau = 1)."""
         self.q_net_target.load_state_dict(self.q_net.state_dict())
@@ -346,6 +354,26 @@ class ImageReplayBuffer(ReplayBuffer):
         return {"external": getattr(self, prefix + "img")[idx], "internal": getattr(self, prefix + "internal")[idx]}
 
 
+def check_ray_buffer(buffer, device) -> None:
+    """What every kernel that walks the replay ring itself assumes of ``buffer`` (``FusedDqnTrainer.train`` and ``train_per``,
+    ``collect.collect_rays``): every field ``capacity`` rows of its dtype, contiguous and on ``device``, flat ray observations,
+    and a sum tree, where there is one, of the buffer's capacity.  ``ValueError`` otherwise, before anything is enqueued."""
+    C = buffer.capacity
+    for name, dtype in (("obs", torch.float32), ("next_obs", torch.float32), ("actions", torch.int64),
+                        ("rewards", torch.float32), ("dones", torch.float32)):
+        x = getattr(buffer, name, None)
+        if x is None or x.dtype != dtype or not x.is_contiguous() or x.device != device or x.shape[0] != C:
+            raise ValueError(f"buffer.{name} must be {C} rows of contiguous {dtype} on {device}")
+    if buffer.obs.shape[1:] != (OBS_DIM,) or buffer.next_obs.shape != buffer.obs.shape:
+        raise ValueError(f"the buffer holds observations of shape {tuple(buffer.obs.shape[1:])}, not ({OBS_DIM},)")
+    tree = getattr(buffer, "sum_tree", None)
+    if tree is not None:
+        t = tree.tree
+        if tree.capacity != C or t.dtype != torch.float64 or not t.is_contiguous() or t.device != device or t.numel() != 2 * C - 1:
+            raise ValueError(f"the sum tree must be {2 * C - 1} contiguous float64 values on {device}: the buffer's capacity is {C}, "
+                             f"the tree's {tree.capacity}")
+
+
 def _map_obs(fn, obs):
     """``fn`` of an observation the loop stands at: a tensor (rays), a dictionary of tensors (images) or None (no loop yet)."""
     if obs is None:
@@ -445,7 +473,8 @@ class DqnLearner:
         self.ep_count, self.ep_return_sum, self.ep_success_sum = (torch.zeros((), dtype=torch.float64, device=self.device) for _ in range(3))
         if use_graph:
             self.trainer.enable_graph(batch_size, weighted=self.per)
-        # decided once: one step's update, and whether a round is ONE launch that samples the buffer itself (fused, one rank, uniform or per_in_kernel)
+        # decided once: one step's update, whether a round is ONE launch that samples the buffer itself (fused, one rank, uniform
+        # or per_in_kernel), and with that the round's update; the round's collection at the end of the constructor
         self._update = self.trainer.update_graphed if use_graph else self.trainer.update
         self.per_in_kernel = bool(per_in_kernel)
         if self.per_in_kernel and self.trainer.collective:
@@ -453,6 +482,7 @@ class DqnLearner:
                              "around the all-reduce")
         self._one_launch = self.fused and (not self.per or self.per_in_kernel) and not self.trainer.collective
         self._train = self.trainer.train_per if self.per_in_kernel else getattr(self.trainer, "train", None)
+        self._update_round = self._update_in_one_launch if self._one_launch else self._update_step_by_step
         # state of the collection loop between two learn() calls (a run can be checkpointed and resumed in the middle)
         self._obs, self._ep_return, self.n_updates = None, None, 0
         self._last_loss = torch.zeros((), device=self.device)
@@ -467,6 +497,7 @@ class DqnLearner:
             # not the trainer's fused_seed (seed + rank): minibatch rows and exploration must not share a stream
             self.collect_seed, self.collect_serial = ((seed + rank) ^ 0x436F6C6C65637421) % 2 ** 64, 0
             self._collect_out = None
+        self._collect = self._collect_in_kernel if self.collect_in_kernel else self._collect_on_host
 
     def _prepare(self, obs):
         """The network's input: the flat vector for rays, the dictionary itself for images."""
@@ -533,38 +564,78 @@ class DqnLearner:
         """The policy alone (the reference's final_model / best_model): the Q-network's weights."""
         torch.save(self.trainer.q_net.state_dict(), path)
 
-    def _collect_round(self, total_timesteps: int, ep_return: torch.Tensor) -> int:
-        """One round's steps inside the step kernel (``collect_in_kernel``): the steps the host-driven loop would make, with its
-        epsilons, in launches of ``collect_launch_steps``; then the episode statistics from the [T, B] outputs in the order
-        (t, then b ascending), and one target sync if any of the round's steps is due one.  Returns the transitions collected."""
+    def _account_episodes(self, done: torch.Tensor, success: torch.Tensor, episode_return: torch.Tensor) -> None:
+        """The episodes that ended in ``done`` ([B] of one step or [T, B] of one launch: t, then b ascending) into the tracked
+        lists or the two device counts, which are sums of integers and exact in float64 in any order.  ``ep_return_sum`` is each
+        round's own: its per-step sums are formed from different tensors and keep their bits only as they stand."""
+        if self.track_episodes:
+            if bool(done.any()):
+                self.episode_returns += episode_return[done].tolist()
+                self.episode_successes += success[done].tolist()
+        else:
+            self.ep_count += done.sum()
+            self.ep_success_sum += (success & done).sum()
+
+    def _sync_due(self, since: int, until: int) -> bool:
+        """Whether one of the environment calls ``since + 1 .. until`` reaches ``target_update_interval`` (in calls of B steps)."""
+        every = max(self.target_update_interval // self.env.B, 1)
+        return any(call % every == 0 for call in range(since + 1, until + 1))
+
+    # ---- the two collection rounds, one of them bound as ``_collect`` in __init__: up to ``train_freq`` calls of the environment with
+    # the schedule's epsilons, buffer rows, episode statistics, counters and the target sync.  Both return the transitions collected.
+    def _collect_on_host(self, total_timesteps: int) -> int:
+        """One round driven from the host: act, auto-reset step and ``buffer.add`` per call, the sync at the call that is due one."""
+        env, B, collected = self.env, self.env.B, 0
+        obs, ep_return = self._obs, self._ep_return
+        for _ in range(self.train_freq):
+            eps = exploration_rate(self.num_timesteps, total_timesteps, *self.eps)
+            actions = self.act(obs, eps)
+            nxt, reward, terminated, truncated, info = env.step(actions, auto_reset=True)
+            done = terminated | truncated
+            nxt_flat = self._prepare(nxt)
+            # the transition stores the observation the episode ended in, not the first one of the next episode;
+            # a time-limit truncation is not a terminal state for the bootstrap (SB3 handle_timeout_termination)
+            stored_next = self._prepare(info["terminal_observation"]) if "terminal_observation" in info else nxt_flat
+            self.buffer.add(obs, stored_next, actions, reward, terminated)
+            ep_return += reward
+            self._account_episodes(done, info["success"], ep_return)
+            if not self.track_episodes:
+                self.ep_return_sum += (ep_return * done).sum()
+            ep_return = torch.where(done, torch.zeros_like(ep_return), ep_return)
+            obs = nxt_flat
+            self.num_timesteps += B
+            self.n_calls += 1
+            collected += B
+            if self._sync_due(self.n_calls - 1, self.n_calls):
+                self.trainer.sync_target()
+            if self.num_timesteps >= total_timesteps:
+                break
+        self._obs, self._ep_return = obs, ep_return
+        return collected
+
+    def _collect_in_kernel(self, total_timesteps: int) -> int:
+        """One round inside the step kernel (``collect_in_kernel``): the steps the host-driven round would make, with its
+        epsilons, in launches of ``collect_launch_steps``; the episode statistics from the [T, B] outputs, and ONE target sync
+        behind the round if any of its steps is due one."""
         from . import collect
-        B = self.env.B
+        B, ep_return = self.env.B, self._ep_return
         n = min(self.train_freq, -(-(total_timesteps - self.num_timesteps) // B))
-        state = getattr(self.trainer, "state", None)      # the fused state block begins with theta
-        theta = state if isinstance(state, torch.Tensor) else torch.cat(
-            [p.detach().reshape(-1) for p in self.trainer.q_net.parameters()]).to(device=self.device, dtype=torch.float32).contiguous()
+        theta = self.trainer.theta()
         if self._collect_out is None:
             self._collect_out = {name: torch.zeros(self.collect_launch_steps, B, dtype=dtype, device=self.device)
                                  for name, dtype in collect.OUTPUTS}
-        every, sync, made = max(self.target_update_interval // B, 1), False, 0
+        sync, made = False, 0
         while made < n:
             T = min(n - made, self.collect_launch_steps)
             eps = [exploration_rate(self.num_timesteps + t * B, total_timesteps, *self.eps) for t in range(T)]
             out = {name: x[:T] for name, x in self._collect_out.items()}
             collect.collect_rays(self.env, theta, self.buffer, eps, self.collect_seed, self.collect_serial, ep_return, out)
-            done, success = out["done"].bool(), out["success"].bool()
-            if self.track_episodes:
-                if bool(done.any()):
-                    self.episode_returns += out["episode_return"][done].tolist()
-                    self.episode_successes += success[done].tolist()
-            else:
-                # the two counts are sums of integers, exact in float64 in any order: one reduction per launch; the returns are
-                # summed per step, as the host-driven loop sums them, so the sum keeps its bits whatever the launch size
-                self.ep_count += done.sum()
-                self.ep_success_sum += (success & done).sum()
+            done, ended = out["done"].bool(), out["episode_return"]
+            self._account_episodes(done, out["success"].bool(), ended)
+            if not self.track_episodes:       # per step, as the host-driven round sums: the same bits whatever the launch size
                 for t in range(T):
-                    self.ep_return_sum += torch.where(done[t], out["episode_return"][t], torch.zeros_like(ep_return)).sum()
-            sync = sync or any((self.n_calls + t + 1) % every == 0 for t in range(T))
+                    self.ep_return_sum += torch.where(done[t], ended[t], torch.zeros_like(ep_return)).sum()
+            sync = sync or self._sync_due(self.n_calls, self.n_calls + T)
             self.collect_serial += T
             self.num_timesteps += T * B
             self.n_calls += T
@@ -573,65 +644,42 @@ class DqnLearner:
             self.trainer.sync_target()
         return n * B
 
+    # ---- the two update rounds, one of them bound as ``_update_round`` in __init__: ``steps`` >= 1 gradient steps -> the last loss
+    def _update_in_one_launch(self, steps: int) -> torch.Tensor:
+        """The round as ONE launch that draws its minibatches itself (``train``, or ``train_per`` with ``per_in_kernel``)."""
+        return self._train(self.buffer, steps, self.batch_size)[-1]
+
+    def _update_step_by_step(self, steps: int) -> torch.Tensor:
+        """Sample, update (eager, a replayed graph or the fused kernel: ``_update``), re-prioritize, ``steps`` times."""
+        for _ in range(steps):
+            batch = self.buffer.sample(self.batch_size, self.gen)
+            loss = self._update(batch)
+            if self.per:      # the PER kernels run eagerly on the same stream, around the (possibly replayed) update
+                self.buffer.update_priorities(batch["indices"], self.trainer.last_td_error)
+        return loss
+
     def learn(self, total_timesteps: int, callback: Optional[Callable[["DqnLearner"], None]] = None,
               stop_at: Optional[int] = None) -> Dict[str, float]:
         """Collect and learn until ``total_timesteps`` (the horizon of the exploration schedule) -- or until ``stop_at``, a
         point to checkpoint at; a later call, also on a learner restored with ``load``, continues exactly there."""
-        env, B = self.env, self.env.B
         if self._obs is None:
-            self._obs = self._prepare(env.reset())
-            self._ep_return = torch.zeros(B, dtype=torch.float64, device=self.device)
-        obs, ep_return, n_updates, last_loss = self._obs, self._ep_return, self.n_updates, self._last_loss
+            self._obs = self._prepare(self.env.reset())
+            self._ep_return = torch.zeros(self.env.B, dtype=torch.float64, device=self.device)
         end = total_timesteps if stop_at is None else min(stop_at, total_timesteps)
         while self.num_timesteps < end:
-            collected = self._collect_round(total_timesteps, ep_return) if self.collect_in_kernel else 0
-            for _ in range(0 if self.collect_in_kernel else self.train_freq):
-                eps = exploration_rate(self.num_timesteps, total_timesteps, *self.eps)
-                actions = self.act(obs, eps)
-                nxt, reward, terminated, truncated, info = env.step(actions, auto_reset=True)
-                done = terminated | truncated
-                nxt_flat = self._prepare(nxt)
-                # the transition stores the observation the episode ended in, not the first one of the next episode;
-                # a time-limit truncation is not a terminal state for the bootstrap (SB3 handle_timeout_termination)
-                stored_next = self._prepare(info["terminal_observation"]) if "terminal_observation" in info else nxt_flat
-                self.buffer.add(obs, stored_next, actions, reward, terminated)
-                ep_return += reward
-                if self.track_episodes:
-                    if bool(done.any()):
-                        self.episode_returns += ep_return[done].tolist()
-                        self.episode_successes += info["success"][done].tolist()
-                else:
-                    self.ep_count += done.sum()
-                    self.ep_return_sum += (ep_return * done).sum()
-                    self.ep_success_sum += (info["success"] & done).sum()
-                ep_return = torch.where(done, torch.zeros_like(ep_return), ep_return)
-                obs = nxt_flat
-                self.num_timesteps += B
-                self.n_calls += 1
-                collected += B
-                if self.n_calls % max(self.target_update_interval // B, 1) == 0:
-                    self.trainer.sync_target()
-                if self.num_timesteps >= total_timesteps:
-                    break
+            collected = self._collect(total_timesteps)
             if self.num_timesteps > self.learning_starts and self.buffer.size >= self.batch_size:
                 steps = self.gradient_steps if self.gradient_steps >= 0 else collected
-                if self._one_launch and steps > 0:
-                    last_loss = self._train(self.buffer, steps, self.batch_size)[-1]
-                for _ in range(0 if self._one_launch else steps):
-                    batch = self.buffer.sample(self.batch_size, self.gen)
-                    last_loss = self._update(batch)       # eager, a replayed graph or the fused kernel: bound in __init__
-                    if self.per:      # the PER kernels run eagerly on the same stream, around the (possibly replayed) update
-                        self.buffer.update_priorities(batch["indices"], self.trainer.last_td_error)
-                n_updates += steps
-            self._obs, self._ep_return, self.n_updates, self._last_loss = obs, ep_return, n_updates, last_loss
+                if steps > 0:
+                    self._last_loss = self._update_round(steps)
+                self.n_updates += steps
             if callback is not None:
                 callback(self)
+        stats = dict(timesteps=self.num_timesteps, updates=self.n_updates, loss=float(self._last_loss))
         if not self.track_episodes:       # whole-run averages from the device counters
             n = float(self.ep_count)
-            return dict(timesteps=self.num_timesteps, updates=n_updates, loss=float(last_loss), episodes=int(n),
-                        mean_return=float(self.ep_return_sum) / n if n else float("nan"),
+            return dict(stats, episodes=int(n), mean_return=float(self.ep_return_sum) / n if n else float("nan"),
                         success_rate=float(self.ep_success_sum) / n if n else float("nan"))
         recent = self.episode_returns[-100:]
-        return dict(timesteps=self.num_timesteps, updates=n_updates, loss=float(last_loss), episodes=len(self.episode_returns),
-                    mean_return=float(sum(recent) / len(recent)) if recent else float("nan"),
+        return dict(stats, episodes=len(self.episode_returns), mean_return=float(sum(recent) / len(recent)) if recent else float("nan"),
                     success_rate=float(sum(self.episode_successes[-100:]) / max(1, len(self.episode_successes[-100:]))))
