@@ -1,7 +1,9 @@
 """The visibility-graph planner kernel (csrc/plangpu.hip) on the GPU: bitwise against its twin
-(tests/support/plan_numpy.py) on the fixture, on seeded random maps and at its limits; batch independence; and
-``BatchedRaysEnv.replace_maps`` / ``BatchedImgsEnv.replace_maps`` with planned maps."""
+(tests/support/plan_numpy.py) on the fixture, on seeded random maps and at its limits -- the largest graphs (N = 255), exact
+ties between lanes, exact contacts, malformed records; batch independence; and ``BatchedRaysEnv.replace_maps`` /
+``BatchedImgsEnv.replace_maps`` with planned maps."""
 import importlib
+import math
 
 import numpy as np
 import pytest
@@ -89,15 +91,44 @@ def test_a_257_vertex_map_is_refused_before_launch(planner):
 
 
 def test_a_malformed_record_is_status_4_and_touches_nothing_else(planner):
-    maps = random_maps(5, 3)
-    rec, caps = path_plan.pack_rings([m[0] for m in maps])
-    rec[1, 2] = 400.0                                    # a ring size beyond the table
-    sg = np.array([np.concatenate([m[1], m[2]]) for m in maps])
-    status, n_nodes, nodes, length = planner.plan_dev(torch.from_numpy(rec).cuda(), torch.from_numpy(sg).cuda(), **caps)
-    good = plan_on_gpu(planner, maps)
-    assert status.cpu().tolist() == [int(good[0][0]), 4, int(good[0][2])]
-    assert n_nodes[1].item() == 0 and not nodes[1].any().item() and length[1].item() == 0.0
-    assert np.array_equal(length.cpu().numpy()[[0, 2]], good[2][[0, 2]])
+    """Good rows alternate with rows that are wrong in one way each.  Every wrong count is refused by a floating-point
+    comparison before it is cast or used as an index (plangpu.hip, phase 1)."""
+    maps = random_maps(5, 12)
+    good, caps = path_plan.pack_rings([m[0] for m in maps])
+    sg_good = np.array([np.concatenate([m[1], m[2]]) for m in maps])
+    V, R = caps["n_vert_max"], caps["n_ring_max"]
+    n_rings, n_vert = int(good[0, 0]), int(good[0, 1])
+    assert n_rings >= 2 and n_vert >= 4
+    # what is wrong -> {position in the record: value}; [0] ring count, [1] vertex count, [2 + k] size of ring k
+    wrong = {"ring count 0": {0: 0.0}, "ring count n_ring_max + 1": {0: R + 1.0}, "ring count nan": {0: math.nan},
+             "vertex count 2": {1: 2.0}, "vertex count nan": {1: math.nan},
+             "a ring size of 2": {2: 2.0}, "a ring size of nan": {3: math.nan}, "a ring size of 1e300": {2: 1e300},
+             "a ring size beyond the table": {2: 400.0},
+             "ring sizes that are valid one by one and sum past n_vert_max": {1: V, **{2 + k: V for k in range(n_rings)}},
+             "a vertex count that differs from the sum": {1: n_vert - 1.0}}
+    rec, sg, kind = [], [], []                           # kind: the good map's number, or what is wrong
+    for b, edits in zip(range(len(maps)), list(wrong.items()) + [None]):
+        rec.append(good[b])
+        sg.append(sg_good[b])
+        kind.append(b)
+        if edits is not None:
+            bad = good[b].copy()
+            for at, value in edits[1].items():
+                bad[at] = value
+            rec.append(bad)
+            sg.append(sg_good[b])
+            kind.append(edits[0])
+    assert len(rec) == 12 + 11 and kind.count(0) == 1
+    out = planner.plan_dev(torch.from_numpy(np.stack(rec)).cuda(), torch.from_numpy(np.stack(sg)).cuda(), **caps)
+    status, n_nodes, nodes, length = (t.cpu().numpy() for t in out)
+    for row, k in enumerate(kind):
+        if isinstance(k, str):
+            assert status[row] == 4 and n_nodes[row] == 0 and length[row] == 0.0 and not nodes[row].any(), k
+            continue
+        alone = planner.plan_dev(torch.from_numpy(good[k:k + 1].copy()).cuda(), torch.from_numpy(sg_good[k:k + 1].copy()).cuda(), **caps)
+        a_status, a_n, a_nodes, a_length = (t.cpu().numpy() for t in alone)
+        assert status[row] == a_status[0] == 0 and n_nodes[row] == a_n[0] >= 2, row
+        assert np.array_equal(nodes[row], a_nodes[0]) and length[row:row + 1].view(np.int64) == a_length.view(np.int64), row
 
 
 def test_batch_independence(planner):
@@ -110,6 +141,105 @@ def test_batch_independence(planner):
     assert alone[0][0] == inside[0][300] == 0 and alone[1][0] == inside[1][300]
     assert alone[2][:1].view(np.int64) == inside[2][300:301].view(np.int64)
     assert np.array_equal(alone[3][0], inside[3][300])
+
+
+# ---- the largest graphs, exact ties, exact contacts ----------------------------------------------------------------------------
+def plan_rows(planner, maps, n_vert_max=None, n_ring_max=None):
+    """One launch -> (status, n_nodes, nodes [B, 64, 2], length) as numpy, and the capacities used."""
+    rec, caps = path_plan.pack_rings([m[0] for m in maps], n_vert_max, n_ring_max)
+    sg = np.array([np.concatenate([m[1], m[2]]) for m in maps])
+    out = planner.plan_dev(torch.from_numpy(rec).cuda(), torch.from_numpy(sg).cuda(), **caps)
+    return tuple(t.cpu().numpy() for t in out), caps
+
+
+def assert_rows_equal_recorded(got, rows, fx, where=None):
+    """Rows ``rows`` of a launch against rows ``where`` (default: all, in order) of a recorded twin fixture, bit for bit."""
+    status, n_nodes, nodes, length = got
+    where = range(len(fx["twin_status"])) if where is None else where
+    for row, i in zip(rows, where):
+        assert status[row] == fx["twin_status"][i] and n_nodes[row] == fx["twin_n_nodes"][i], (row, i)
+        assert length[row:row + 1].view(np.int64) == fx["twin_length"][i:i + 1].view(np.int64), (row, i)
+        # all 128 doubles: the path where the status is 0, zeros behind it and in every other row
+        assert np.array_equal(nodes[row], fx["twin_nodes"][i]), (row, i)
+        if status[row] != 0:
+            assert not nodes[row].any(), (row, i)
+
+
+def test_all_limit_maps_in_one_launch_equal_the_recorded_twin(planner):
+    """N = 255 (adjacency words 0 .. 7, four nodes per lane, compaction past rank 64), paths through graph index 251,
+    NO_PATH after 121 settled nodes, the six ties -- with the 12 small fixture maps in between, so that a large graph's
+    neighbours in the launch are small ones."""
+    named, fx = plan_maps.limit_maps(), plan_maps.limits_fixture()
+    _, small, small_fx = plan_maps.fixture()
+    maps, big_rows, small_rows = [], [], []
+    for i, (_, m) in enumerate(named):
+        big_rows.append(len(maps))
+        maps.append(m)
+        if i < len(small):
+            small_rows.append(len(maps))
+            maps.append(small[i])
+    got, caps = plan_rows(planner, maps)
+    assert caps == dict(n_vert_max=256, n_ring_max=32) and len(small_rows) == 12
+    print("status:", got[0].tolist())
+    assert_rows_equal_recorded(got, big_rows, fx)
+    assert_rows_equal_recorded(got, small_rows, small_fx)
+    assert np.bincount(got[0][big_rows], minlength=5).tolist() == [15, 1, 1, 1, 0]
+
+
+@pytest.mark.parametrize("name", ["saw_hall(60, 40)", "tie_square(7, 8, 7)"])
+def test_tight_capacities_and_both_paddings_of_the_record(planner, name):
+    """Alone at the tightest capacities, and with one ring more: the record is 2 + R + 2 V doubles padded to an even count
+    and the coordinates start at 2 + n_ring_max, so one of the two is padded and the other is not."""
+    named, fx = plan_maps.limit_maps(), plan_maps.limits_fixture()
+    i = [n for n, _ in named].index(name)
+    m = named[i][1]
+    V, R = sum(len(r) for r in m[0]), len(m[0])
+    lengths = []
+    for n_ring_max in (R, R + 1):
+        got, caps = plan_rows(planner, [m], n_ring_max=n_ring_max)
+        assert caps == dict(n_vert_max=V, n_ring_max=n_ring_max)
+        lengths.append(path_plan.record_doubles(V, n_ring_max))
+        assert got[0][0] == 0
+        assert_rows_equal_recorded(got, [0], fx, [i])
+    assert lengths[0] == lengths[1] == 2 + R + 1 + 2 * V                          # R padded, R + 1 not
+
+
+def test_n_node_max_on_both_sides_of_a_path(planner):
+    fx = plan_maps.limits_fixture()
+    saw = plan_maps.saw_hall(60, 40)
+    i = fx["names"].tolist().index("saw_hall(60, 40)")
+    assert fx["twin_n_nodes"][i] == 42
+    got, _ = plan_rows(path_plan.PathPlanner(device=0, n_node_max=42), [saw])
+    assert_rows_equal_recorded(got, [0], fx, [i])
+    (status, n_nodes, nodes, length), _ = plan_rows(path_plan.PathPlanner(device=0, n_node_max=41), [saw])
+    assert status[0] == 3 and n_nodes[0] == 42 and length[0] == 0.0 and not nodes[0].any()
+    empty = (path_plan.oriented_rings(plan_maps.ROOM, []), np.array([1.0, 2.0]), np.array([9.0, 7.5]))
+    one_bend = (path_plan.oriented_rings(plan_maps.ROOM, [plan_maps.box(3, 2, 7, 6)]), np.array([1.0, 1.0]), np.array([9.0, 8.0]))
+    (status, n_nodes, nodes, length), _ = plan_rows(path_plan.PathPlanner(device=0, n_node_max=2), [empty, one_bend])
+    assert status.tolist() == [0, 3] and n_nodes.tolist() == [2, 3]
+    assert nodes[0, :2].tolist() == [[1.0, 2.0], [9.0, 7.5]] and length[0] == math.sqrt(8.0 * 8.0 + 5.5 * 5.5)
+    assert not nodes[0, 2:].any() and not nodes[1].any() and length[1] == 0.0
+
+
+def test_exact_contacts_on_the_kernel(planner):
+    cases = plan_maps.contact_cases()
+    status, n_nodes, length, paths = assert_equals_twin(planner, [c[1] for c in cases])
+    for b, (name, _, want_status, want_nodes, want_length) in enumerate(cases):
+        assert status[b] == want_status and np.array_equal(paths[b], want_nodes) and length[b] == want_length, name
+        assert n_nodes[b] == len(want_nodes), name
+
+
+def test_batch_independence_at_size(planner):
+    """The largest graph alone and as row 300 of 512."""
+    probe = plan_maps.field_of_polygons(3)
+    maps = random_maps(12, 511)
+    alone, _ = plan_rows(planner, [probe])
+    inside, caps = plan_rows(planner, maps[:300] + [probe] + maps[300:])
+    assert caps == dict(n_vert_max=256, n_ring_max=32) and len(inside[0]) == 512
+    assert alone[0][0] == inside[0][300] == 0 and alone[1][0] == inside[1][300] == 3
+    assert alone[3][:1].view(np.int64) == inside[3][300:301].view(np.int64)
+    assert np.array_equal(alone[2][0], inside[2][300])
+    assert max(plan_maps.graph_indices(probe[0], alone[2][0, 1:2])) >= 224
 
 
 # ---- replace_maps -----------------------------------------------------------------------------------------------------------

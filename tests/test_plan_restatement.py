@@ -1,6 +1,7 @@
 """The visibility-graph planner without a GPU: analytic cases of the twin (tests/support/plan_numpy.py), the
-twin against an independent brute-force check (tests/support/plan_bruteforce.py), ``rl_geometry.mitre_polygon``, and the
-C header against ``path_plan.PLAN_EXPORTS`` and the built library."""
+twin against an independent brute-force check (tests/support/plan_bruteforce.py), the maps at the kernel's limits (how they
+are built, the twin against their recorded results, which branches of the contact rule they reach),
+``rl_geometry.mitre_polygon``, and the C header against ``path_plan.PLAN_EXPORTS`` and the built library."""
 import ctypes
 import importlib
 import math
@@ -10,6 +11,7 @@ import re
 import numpy as np
 import pytest
 
+from tests.support import plan_branches
 from tests.support import plan_bruteforce as brute
 from tests.support import plan_maps
 from tests.support import plan_numpy as twin
@@ -156,6 +158,173 @@ def test_twin_equals_bruteforce_on_seeded_random_dynamic_maps():
 
 def test_twin_equals_bruteforce_on_a_ring_of_boxes_across_the_boundary():
     check_against_bruteforce(*plan_maps.comb_of_boxes(7))
+
+
+# ---- the maps at the kernel's limits ------------------------------------------------------------------------------------------
+# Of the recorded results (tests/golden/planner_limits.npz) the twin recomputes here: every saw_hall, walled_field, every
+# tie_square, and these two of the eight field pairs (4 s each; pair 3 bends at graph index 251, pair 1 at 214).  The other
+# six field pairs and every brute-force length are read from the file.
+LIVE_FIELD_PAIRS = (1, 3)
+
+
+@pytest.fixture(scope="module")
+def limits():
+    """names, maps and recorded results of the limit set; ``live``: name -> the twin's result, computed now; ``counts``: the
+    contact-rule branches those runs reached (field pairs are not counted: their coordinates are jittered, no contact in
+    them is exact -- near_collinear_triples == 0 is asserted below)."""
+    named = plan_maps.limit_maps()
+    fx = plan_maps.limits_fixture()
+    counts = plan_branches.new_counter()
+    live = {}
+    for name, m in named:
+        if name.startswith("field_of_polygons"):
+            if name in [f"field_of_polygons({q})" for q in LIVE_FIELD_PAIRS]:
+                live[name] = twin.plan(*m)
+            continue
+        plan_branches.count_table(*m, counts)
+        with plan_branches.counting_twin(counts):
+            live[name] = twin.plan(*m)
+    rows = {name: i for i, (name, _) in enumerate(named)}
+    return dict(named=named, maps=dict(named), fx=fx, live=live, counts=counts, rows=rows)
+
+
+def recorded(limits, name):
+    fx, i = limits["fx"], limits["rows"][name]
+    n = int(fx["twin_n_nodes"][i]) if fx["twin_status"][i] == twin.OK else 0
+    return int(fx["twin_status"][i]), int(fx["twin_n_nodes"][i]), fx["twin_nodes"][i, :n], float(fx["twin_length"][i])
+
+
+def recorded_bends(limits, name):
+    """Graph indices of the bends of the recorded path."""
+    return plan_maps.graph_indices(limits["maps"][name][0], recorded(limits, name)[2][1:-1])
+
+
+def test_field_of_polygons_is_the_largest_graph_and_its_paths_reach_the_highest_indices(limits):
+    rings = plan_maps.field_of_polygons(0)[0]
+    assert sum(len(r) for r in rings) == 256 and len(rings) == 32
+    assert sorted(len(r) for r in rings[1:]) == [8] * 26 + [9] * 5 and len(rings[0]) == 3
+    assert plan_maps.n_graph_nodes(rings) == 255                     # every obstacle vertex; 255 is the maximum (docstring)
+    status, highest = [], []
+    for q in range(plan_maps.N_FIELD_PAIRS):
+        name = f"field_of_polygons({q})"
+        assert brute.near_collinear_triples(*limits["maps"][name]) == 0, name
+        status.append(recorded(limits, name)[0])
+        highest.append(max(recorded_bends(limits, name), default=-1))
+    print("status", status, "highest graph index on each path", highest)
+    assert status[plan_maps.FIELD_NOT_FREE_PAIR] == twin.NOT_FREE and status.count(twin.OK) == 7
+    assert sum(h >= 192 for h in highest) >= 1 and max(highest) >= 224          # adjacency words 6 and 7, a lane's 4th node
+
+
+def test_saw_halls_bend_at_high_indices_and_stand_on_both_sides_of_64_nodes(limits):
+    (rings, _, _), (status, n, _, _) = limits["maps"]["saw_hall(60, 40)"], recorded(limits, "saw_hall(60, 40)")
+    assert sum(len(r) for r in rings) == 244 and plan_maps.n_graph_nodes(rings) == 102 and (status, n) == (twin.OK, 42)
+    assert sorted(recorded_bends(limits, "saw_hall(60, 40)")) == list(range(62, 102))    # ceiling and floor tips take turns
+    (rings, _, _), (status, n, _, _) = limits["maps"]["saw_hall(20, 62)"], recorded(limits, "saw_hall(20, 62)")
+    assert (status, n) == (twin.OK, 64) and min(recorded_bends(limits, "saw_hall(20, 62)")) >= 22
+    (rings, _, _), (status, n, nodes, length) = limits["maps"]["saw_hall(20, 63)"], recorded(limits, "saw_hall(20, 63)")
+    assert sum(len(r) for r in rings) == 2 * 20 + 3 * 63 + 4 == 233
+    assert (status, n) == (twin.TOO_MANY_NODES, 65) and len(nodes) == 0 and length == 0.0
+    # n_node_max on both sides of the 42 nodes
+    m = limits["maps"]["saw_hall(60, 40)"]
+    r = twin.plan(*m, max_nodes=42)
+    assert r["status"] == twin.OK and r["length"] == recorded(limits, "saw_hall(60, 40)")[3]
+    r = twin.plan(*m, max_nodes=41)
+    assert r["status"] == twin.TOO_MANY_NODES and r["n_nodes"] == 42
+
+
+def test_walled_field_is_no_path_after_a_long_search(limits):
+    m = limits["maps"]["walled_field()"]
+    assert plan_maps.n_graph_nodes(m[0]) == 242 >= 130
+    assert plan_maps.reachable_from_start(*m) == 121 >= 65
+    status, n, nodes, length = recorded(limits, "walled_field()")
+    assert (status, n, length) == (twin.NO_PATH, 0, 0.0) and not limits["fx"]["twin_nodes"][limits["rows"]["walled_field()"]].any()
+
+
+# variant -> (lower graph index, its lane), (higher graph index, its lane) of the two tied corners
+TIE_PATTERNS = {"same lane": ((58, 58), (122, 58)), "lower index on the higher lane": ((58, 58), (69, 5)),
+                "lower index on the lower lane": ((66, 2), (77, 13))}
+
+
+def tie_pattern(rings):
+    a, b = plan_maps.graph_indices(rings, [plan_maps.TIE_A, plan_maps.TIE_B])
+    return (a, a & 63), (b, b & 63)
+
+
+@pytest.mark.parametrize("variant", list(plan_maps.TIE_VARIANTS))
+@pytest.mark.parametrize("corner", [7, 3])
+def test_tie_squares_take_the_corner_with_the_lower_graph_index(limits, variant, corner):
+    n_decoy, m = plan_maps.TIE_VARIANTS[variant]
+    name = f"tie_square({n_decoy}, {m}, {corner})"
+    rings = limits["maps"][name][0]
+    square = rings[-1].tolist()
+    assert sorted(square) == sorted([y, x] for x, y in square)                   # mirror-symmetric bit for bit
+    a, b = tie_pattern(rings)
+    low, high = TIE_PATTERNS[variant]
+    assert (b, a) == (low, high) if corner == 7 else (a, b) == (low, high)      # arc at (7, 7): B first; at (3, 3): A first
+    winner = plan_maps.TIE_B if corner == 7 else plan_maps.TIE_A
+    status, n, nodes, length = recorded(limits, name)
+    print(name, "A", a, "B", b, "winner", nodes[1].tolist())
+    assert (status, n) == (twin.OK, 3) and tuple(nodes[1].tolist()) == winner
+    assert length == math.sqrt(40.0) + math.sqrt(40.0)
+
+
+def test_the_twin_equals_its_recorded_results_bit_for_bit(limits):
+    assert len(limits["live"]) == 3 + 1 + 6 + len(LIVE_FIELD_PAIRS)
+    for name, r in limits["live"].items():
+        status, n, nodes, length = recorded(limits, name)
+        assert (r["status"], r["n_nodes"]) == (status, n), name
+        assert np.array_equal(r["nodes"], nodes) and r["length"] == length, name
+
+
+def test_recorded_paths_are_free_and_as_short_as_the_bruteforce_says(limits):
+    fx = limits["fx"]
+    for name, (rings, _, _) in limits["named"]:
+        i = limits["rows"][name]
+        status, n, nodes, length = recorded(limits, name)
+        want = float(fx["brute_length"][i])
+        if status == twin.NOT_FREE:
+            assert math.isnan(want), name
+        elif status == twin.NO_PATH:
+            assert math.isinf(want), name
+        elif status == twin.OK:
+            assert abs(length - want) <= 1e-9 * want, name                       # the bound of check_against_bruteforce
+            for p, q in zip(nodes[:-1], nodes[1:]):
+                assert brute.segment_is_free(p, q, rings), (name, p, q)
+        else:
+            assert status == twin.TOO_MANY_NODES and math.isfinite(want), name
+        assert not fx["twin_nodes"][i, len(nodes):].any()
+
+
+@pytest.mark.parametrize("case", plan_maps.contact_cases(), ids=lambda c: c[0])
+def test_exact_contacts_give_the_path_written_down_and_the_bruteforce_agrees(case):
+    name, m, status, nodes, length = case
+    r = check_against_bruteforce(*m)
+    assert r["status"] == status and r["n_nodes"] == len(nodes)
+    assert np.array_equal(r["nodes"], nodes) and r["length"] == length
+
+
+def test_the_limit_set_reaches_what_it_is_for(limits):
+    """What keeps the set honest: every property below is computed from the set, and each family carries one of them."""
+    counts = limits["counts"].copy()
+    for _, m, *_ in plan_maps.contact_cases():
+        plan_branches.count_map(*m, counts)
+    print("branches reached:", dict(counts))
+    for name in plan_branches.BRANCHES:                                          # without contact_cases(): nine of these are below 5
+        assert counts[name] >= 5, name
+    n_nodes = {name: plan_maps.n_graph_nodes(m[0]) for name, m in limits["named"]}
+    assert max(n_nodes.values()) == 255                                          # field_of_polygons
+    ok = [name for name, _ in limits["named"] if recorded(limits, name)[0] == twin.OK]
+    assert max(max(recorded_bends(limits, name), default=0) for name in ok) >= 224             # field_of_polygons
+    # a path whose every bend lies past index 61, 40 of them (lanes that own a second node), and 64 against 65 nodes: saw_hall
+    assert any(len(b) >= 40 and min(b) >= 62 for b in map(lambda name: recorded_bends(limits, name), ok))
+    assert {64, 65} <= {recorded(limits, name)[1] for name, _ in limits["named"]}
+    # NO_PATH after a search that settled more than a wavefront of nodes: walled_field
+    assert any(recorded(limits, name)[0] == twin.NO_PATH and n_nodes[name] >= 130 and plan_maps.reachable_from_start(*m) >= 65
+               for name, m in limits["named"])
+    # every tie pattern with either corner as the winner: tie_square
+    ties = {(tie_pattern(m[0]), tuple(recorded(limits, name)[2][1].tolist())) for name, m in limits["named"] if name.startswith("tie")}
+    assert {tuple(sorted(p)) for p, _ in ties} == set(TIE_PATTERNS.values())
+    assert len(ties) == 6 and {w for _, w in ties} == {plan_maps.TIE_A, plan_maps.TIE_B}
 
 
 # ---- mitre_polygon ---------------------------------------------------------------------------------------------------------------
