@@ -33,12 +33,11 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 #include <type_traits>
 
 #include "../../include/mpcgpu_dqn.h"
 #include "../../include/mpcgpu_dqn_per.h"
+#include "abi_host.hpp"
 #include "counter_stream.hpp"
 #include "dqn_layout.hpp"
 #include "per_tree.hpp"
@@ -386,22 +385,12 @@ __global__ void __launch_bounds__(NT) dqn_kernel(const Args a, const std::condit
 
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-thread_local std::string g_err;
-int fail(const char* what, hipError_t e = hipSuccess) {
-    char buf[256];
-    if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    else snprintf(buf, sizeof buf, "%s", what);
-    g_err = buf;
-    return -1;
-}
+thread_local abi::ErrorSlot g_err;          // mpcgpu_dqn_last_error
+thread_local abi::ErrorSlot g_err_per;      // mpcgpu_dqn_per_last_error: a slot of its own, a refusal there leaves g_err alone
+int fail(const char* what) { return g_err.fail(what); }
 
-thread_local std::string g_err_per;      // mpcgpu_dqn_per_last_error
-int fail_per(const char* what, hipError_t e = hipSuccess) {
-    fail(what, e);
-    g_err_per.swap(g_err);
-    return -1;
-}
-
+// what every entry that takes mpcgpu_dqn_params says when valid() refuses them
+constexpr const char* BAD_PARAMS = "invalid mpcgpu_dqn_params (lr, max_grad_norm, eps > 0, 0 <= beta < 1, double_q 0 / 1)";
 bool valid(const mpcgpu_dqn_params* p) {
     return p && p->lr > 0.0 && p->max_grad_norm > 0.0 && p->beta1 >= 0.0 && p->beta1 < 1.0 && p->beta2 >= 0.0 && p->beta2 < 1.0 &&
            p->eps > 0.0 && (p->double_q == 0 || p->double_q == 1);
@@ -418,24 +407,25 @@ Args base(const mpcgpu_dqn_params* p) {
     return a;
 }
 
-int launch(int32_t device, const Args& a, void* stream) {
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail("hipSetDevice", e);
-    hipLaunchKernelGGL(dqn_kernel<false>, dim3(1), dim3(NT), 0, (hipStream_t)stream, a, NoTree{});
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("dqn_kernel launch", e);
+// the one place that launches dqn_kernel: Tree = NoTree for the entries of mpcgpu_dqn.h, PerArgs for the prioritized launch
+template <typename Tree>
+int launch(abi::ErrorSlot& slot, int32_t device, const Args& a, const Tree& tr, void* stream) {
+    constexpr bool PER = std::is_same_v<Tree, PerArgs>;
+    if (abi::on_device(slot, device)) return -1;
+    hipLaunchKernelGGL(dqn_kernel<PER>, dim3(1), dim3(NT), 0, (hipStream_t)stream, a, tr);
+    return abi::launched(slot, PER ? "dqn_kernel<PER> launch" : "dqn_kernel launch");
 }
 
 int minibatch(int32_t device, const mpcgpu_dqn_params* params, float* state, const float* obs, const float* next_obs,
               const int64_t* actions, const float* rewards, const float* dones, const float* weights, int32_t n, float* grad,
               float* loss, float* td, int mode, void* stream) {
-    if (!valid(params)) return fail("invalid mpcgpu_dqn_params (lr, max_grad_norm, eps > 0, 0 <= beta < 1, double_q 0 / 1)");
+    if (!valid(params)) return fail(BAD_PARAMS);
     if (n < 1 || n > MPCGPU_DQN_MAX_ROWS) return fail("1 <= n <= 256");
     if (!state || !obs || !next_obs || !actions || !rewards || !dones || !grad || !loss) return fail("null pointer");
     Args a = base(params);
     a.state = state; a.obs = obs; a.next_obs = next_obs; a.actions = actions; a.rewards = rewards; a.dones = dones;
     a.weights = weights; a.grad_out = grad; a.loss = loss; a.td = td; a.n = n; a.mode = mode;
-    return launch(device, a, stream);
+    return launch(g_err, device, a, NoTree{}, stream);
 }
 
 }  // namespace dqngpu
@@ -461,11 +451,11 @@ int32_t mpcgpu_dqn_step_dev(int32_t device, const mpcgpu_dqn_params* params, flo
 int32_t mpcgpu_dqn_apply_dev(int32_t device, const mpcgpu_dqn_params* params, float* state, const float* grad, float scale,
                              void* stream) {
     using namespace dqngpu;
-    if (!valid(params)) return fail("invalid mpcgpu_dqn_params (lr, max_grad_norm, eps > 0, 0 <= beta < 1, double_q 0 / 1)");
+    if (!valid(params)) return fail(BAD_PARAMS);
     if (!state || !grad) return fail("null pointer");
     Args a = base(params);
     a.state = state; a.grad_in = grad; a.scale = scale; a.mode = DO_APPLY;
-    return launch(device, a, stream);
+    return launch(g_err, device, a, NoTree{}, stream);
 }
 
 int32_t mpcgpu_dqn_train_dev(int32_t device, const mpcgpu_dqn_params* params, float* state, const float* buf_obs,
@@ -473,7 +463,7 @@ int32_t mpcgpu_dqn_train_dev(int32_t device, const mpcgpu_dqn_params* params, fl
                              const float* buf_dones, int64_t size, int32_t n, int32_t K, uint64_t seed, uint64_t serial0,
                              float* losses, void* stream) {
     using namespace dqngpu;
-    if (!valid(params)) return fail("invalid mpcgpu_dqn_params (lr, max_grad_norm, eps > 0, 0 <= beta < 1, double_q 0 / 1)");
+    if (!valid(params)) return fail(BAD_PARAMS);
     if (n < 1 || n > MPCGPU_DQN_MAX_ROWS) return fail("1 <= n <= 256");
     if (K < 1 || K > MPCGPU_DQN_MAX_STEPS) return fail("1 <= K <= 65536");
     if (size < 1 || size >= ((int64_t)1 << 31)) return fail("1 <= size < 2^31");
@@ -482,10 +472,10 @@ int32_t mpcgpu_dqn_train_dev(int32_t device, const mpcgpu_dqn_params* params, fl
     a.state = state; a.obs = buf_obs; a.next_obs = buf_next_obs; a.actions = buf_actions; a.rewards = buf_rewards;
     a.dones = buf_dones; a.size = size; a.n = n; a.steps = K; a.seed = seed; a.serial0 = serial0; a.loss = losses;
     a.mode = DO_GRAD | DO_APPLY | DO_SAMPLE;
-    return launch(device, a, stream);
+    return launch(g_err, device, a, NoTree{}, stream);
 }
 
-const char* mpcgpu_dqn_last_error(void) { return dqngpu::g_err.c_str(); }
+const char* mpcgpu_dqn_last_error(void) { return dqngpu::g_err.text.c_str(); }
 
 // ---- include/mpcgpu_dqn_per.h -------------------------------------------------------------------------------------------------
 int32_t mpcgpu_dqn_train_per_dev(int32_t device, const mpcgpu_dqn_params* dqn, const mpcgpu_per_params* per, float* state,
@@ -493,12 +483,13 @@ int32_t mpcgpu_dqn_train_per_dev(int32_t device, const mpcgpu_dqn_params* dqn, c
                                  const float* buf_rewards, const float* buf_dones, int64_t n_entries, int32_t n, int32_t K,
                                  uint64_t seed, uint64_t serial0, float* losses, int64_t* indices, float* td, void* stream) {
     using namespace dqngpu;
-    if (!valid(dqn)) return fail_per("invalid mpcgpu_dqn_params (lr, max_grad_norm, eps > 0, 0 <= beta < 1, double_q 0 / 1)");
-    if (!pergpu::valid(per)) return fail_per("invalid mpcgpu_per_params (capacity 1..2^30, update_max_freq >= 1, alpha, epsilon >= 0, 0 <= beta < inf, initial_priority > 0)");
-    if (n < 1 || n > MPCGPU_DQN_MAX_ROWS) return fail_per("1 <= n <= 256");
-    if (K < 1 || K > MPCGPU_DQN_MAX_STEPS) return fail_per("1 <= K <= 65536");
-    if (n_entries < 1 || n_entries > per->capacity) return fail_per("1 <= n_entries <= capacity");
-    if (!state || !tree || !buf_obs || !buf_next_obs || !buf_actions || !buf_rewards || !buf_dones || !losses) return fail_per("null pointer");
+    abi::ErrorSlot& slot = g_err_per;
+    if (!valid(dqn)) return slot.fail(BAD_PARAMS);
+    if (!pergpu::valid(per)) return slot.fail(pergpu::BAD_PARAMS);
+    if (n < 1 || n > MPCGPU_DQN_MAX_ROWS) return slot.fail("1 <= n <= 256");
+    if (K < 1 || K > MPCGPU_DQN_MAX_STEPS) return slot.fail("1 <= K <= 65536");
+    if (n_entries < 1 || n_entries > per->capacity) return slot.fail("1 <= n_entries <= capacity");
+    if (!state || !tree || !buf_obs || !buf_next_obs || !buf_actions || !buf_rewards || !buf_dones || !losses) return slot.fail("null pointer");
     Args a = base(dqn);
     a.state = state; a.obs = buf_obs; a.next_obs = buf_next_obs; a.actions = buf_actions; a.rewards = buf_rewards;
     a.dones = buf_dones; a.n = n; a.steps = K; a.seed = seed; a.serial0 = serial0; a.loss = losses; a.td = td;
@@ -506,13 +497,9 @@ int32_t mpcgpu_dqn_train_per_dev(int32_t device, const mpcgpu_dqn_params* dqn, c
     PerArgs tr{};
     tr.tree = tree; tr.indices = indices; tr.C = per->capacity; tr.n_entries = n_entries;
     tr.alpha = per->alpha; tr.beta = per->beta; tr.epsilon = per->epsilon;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_per("hipSetDevice", e);
-    hipLaunchKernelGGL(dqn_kernel<true>, dim3(1), dim3(NT), 0, (hipStream_t)stream, a, tr);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_per("dqn_kernel<PER> launch", e);
+    return launch(slot, device, a, tr, stream);
 }
 
-const char* mpcgpu_dqn_per_last_error(void) { return dqngpu::g_err_per.c_str(); }
+const char* mpcgpu_dqn_per_last_error(void) { return dqngpu::g_err_per.text.c_str(); }
 
 }  // extern "C"

@@ -9,8 +9,6 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 #include <type_traits>
 
 #include "../../include/mpcgpu_collect.h"
@@ -552,21 +550,34 @@ __global__ __launch_bounds__(WAVE) void collect_act_kernel(const float* __restri
     }
 }
 
-thread_local std::string g_err;
-int fail(const char* what, hipError_t e) {
-    char buf[256];
-    if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    else snprintf(buf, sizeof buf, "%s", what);
-    g_err = buf;
-    return -1;
-}
+thread_local abi::ErrorSlot g_err;
 
 // what launch_step refuses in the params, or NULL; fills k
 const char* params_error(const mpcgpu_env_params* params, EnvK& k) {
-    if (!params || !layout(*params, k)) return "invalid mpcgpu_env_params (P 2..64, M 0..31, K 1..4, E >= 1)";
+    if (!params || !layout(*params, k)) return BAD_PARAMS;
     if (params->num_segments != NSEG || params->corner_samples != NCORNER)
         return "only num_segments = 8 and corner_samples = 3 are built (rays_reward1.py:18-20)";
     return nullptr;
+}
+
+int autoreset_args(const int32_t* action, int32_t max_episode_steps, bool images) {
+    if (!action)
+        return fail(images ? "auto-reset needs actions (use mpcgpu_env_step_imgs_dev to observe)"
+                           : "auto-reset needs actions (use mpcgpu_env_step_dev to observe)");
+    if (max_episode_steps <= 0) return fail("max_episode_steps must be positive");
+    return 0;
+}
+
+int fresh_args(const EnvFresh& fr, const char* also_bad, const int32_t* action, EnvOut& out) {
+    if (!fr.which || !fr.spare_ready || !fr.loaded || !fr.stale) return fail("null pointer (which / spare_ready / loaded / stale)");
+    if (also_bad) return fail(also_bad);
+    if (out.max_steps < 0) return fail("max_episode_steps must not be negative");
+    if (out.max_steps > 0 && !action) return fail("auto-reset needs actions (max_episode_steps = 0 observes)");
+    if (out.max_steps > 0 && !out.truncated) return fail("null pointer (truncated)");
+    if (out.max_steps == 0) {
+        out.truncated = nullptr; out.term_int = out.term_ext = nullptr; out.pre_reset = nullptr;
+    }
+    return 0;
 }
 
 int launch_step(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records, double* state,
@@ -575,24 +586,18 @@ int launch_step(int32_t device, const mpcgpu_env_params* params, int32_t B, cons
     if (const char* bad = params_error(params, k)) return fail(bad);
     if (B < 0 || !records || !state || !out.obs_int || (need_ext && !out.obs_ext)) return fail("null pointer / negative batch");
     if (B == 0) return 0;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail("hipSetDevice", e);
+    if (abi::on_device(g_err, device)) return -1;
     if (fresh)
         hipLaunchKernelGGL(env_step_kernel<true>, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state, action, out,
                            (int)B, *fresh, NoCollect{});
     else
         hipLaunchKernelGGL(env_step_kernel<false>, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state, action, out,
                            (int)B, EnvFresh{}, NoCollect{});
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail("env_step_kernel launch", e);
-    return 0;
+    return abi::launched(g_err, "env_step_kernel launch");
 }
 
-thread_local std::string g_collect_err;
-int collect_fail(const char* what, hipError_t e = hipSuccess) {
-    g_collect_err = e != hipSuccess ? std::string(what) + ": " + hipGetErrorString(e) : std::string(what);
-    return -1;
-}
+thread_local abi::ErrorSlot g_collect_err;   // mpcgpu_collect_last_error
+int collect_fail(const char* what) { return g_collect_err.fail(what); }
 bool eps_ok(double eps) { return eps >= 0.0 && eps <= 1.0; }   // false for NaN
 
 }  // namespace envgpu
@@ -601,7 +606,7 @@ extern "C" {
 
 int32_t mpcgpu_env_record_doubles(const mpcgpu_env_params* params) {
     envgpu::EnvK k;
-    if (!params || !envgpu::layout(*params, k)) return envgpu::fail("invalid mpcgpu_env_params (P 2..64, M 0..31, K 1..4, E >= 1)");
+    if (!params || !envgpu::layout(*params, k)) return envgpu::fail(envgpu::BAD_PARAMS);
     return k.rec;
 }
 
@@ -616,14 +621,13 @@ int32_t mpcgpu_env_step_autoreset_dev(int32_t device, const mpcgpu_env_params* p
                                       double* state, const int32_t* action, float* obs_internal, float* obs_external,
                                       double* reward, uint8_t* terminated, uint8_t* truncated, float* terminal_obs_internal,
                                       float* terminal_obs_external, int32_t max_episode_steps, void* stream) {
-    if (!action) return envgpu::fail("auto-reset needs actions (use mpcgpu_env_step_dev to observe)");
-    if (max_episode_steps <= 0) return envgpu::fail("max_episode_steps must be positive");
+    if (envgpu::autoreset_args(action, max_episode_steps, false)) return -1;
     envgpu::EnvOut out{obs_internal, obs_external, reward, terminated, truncated, terminal_obs_internal,
                        terminal_obs_external, max_episode_steps, nullptr};
     return envgpu::launch_step(device, params, B, records, state, action, out, true, stream);
 }
 
-const char* mpcgpu_env_last_error(void) { return envgpu::g_err.c_str(); }
+const char* mpcgpu_env_last_error(void) { return envgpu::g_err.text.c_str(); }
 
 // include/mpcgpu_map.h
 int32_t mpcgpu_env_step_fresh_dev(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records2,
@@ -631,14 +635,10 @@ int32_t mpcgpu_env_step_fresh_dev(int32_t device, const mpcgpu_env_params* param
                                   const int32_t* action, float* obs_internal, float* obs_external, double* reward,
                                   uint8_t* terminated, uint8_t* truncated, float* terminal_obs_internal,
                                   float* terminal_obs_external, int32_t max_episode_steps, void* stream) {
-    if (!which || !spare_ready || !loaded || !stale) return envgpu::fail("null pointer (which / spare_ready / loaded / stale)");
-    if (max_episode_steps < 0) return envgpu::fail("max_episode_steps must not be negative");
-    if (max_episode_steps > 0 && !action) return envgpu::fail("auto-reset needs actions (max_episode_steps = 0 observes)");
-    if (max_episode_steps > 0 && !truncated) return envgpu::fail("null pointer (truncated)");
-    envgpu::EnvOut out{obs_internal, obs_external, reward, terminated, max_episode_steps > 0 ? truncated : nullptr,
-                       max_episode_steps > 0 ? terminal_obs_internal : nullptr,
-                       max_episode_steps > 0 ? terminal_obs_external : nullptr, max_episode_steps, nullptr};
+    envgpu::EnvOut out{obs_internal, obs_external, reward, terminated, truncated, terminal_obs_internal,
+                       terminal_obs_external, max_episode_steps, nullptr};
     const envgpu::EnvFresh fresh{which, spare_ready, loaded, stale};
+    if (envgpu::fresh_args(fresh, nullptr, action, out)) return -1;
     return envgpu::launch_step(device, params, B, records2, state, action, out, true, stream, &fresh);
 }
 
@@ -654,13 +654,10 @@ int32_t mpcgpu_collect_act_dev(int32_t device, const float* theta, const float* 
     if (B < 0) return collect_fail("negative batch");
     if (!eps_ok(eps)) return collect_fail("eps must lie in [0, 1]");
     if (B == 0) return 0;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return collect_fail("hipSetDevice", e);
+    if (abi::on_device(g_collect_err, device)) return -1;
     hipLaunchKernelGGL(collect_act_kernel, dim3(B < 1024 ? B : 1024), dim3(WAVE), 0, (hipStream_t)stream, theta, obs_external,
                        obs_internal, (int)B, eps, seed, serial, actions, q);
-    e = hipGetLastError();
-    if (e != hipSuccess) return collect_fail("collect_act_kernel launch", e);
-    return 0;
+    return abi::launched(g_collect_err, "collect_act_kernel launch");
 }
 
 int32_t mpcgpu_collect_rays_dev(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records, double* state,
@@ -688,19 +685,16 @@ int32_t mpcgpu_collect_rays_dev(int32_t device, const mpcgpu_env_params* params,
     for (int t = 0; t < collect->T; ++t)
         if (!eps_ok(collect->eps[t])) return collect_fail("every eps[t], t < T, must lie in [0, 1]");
     if (B == 0) return 0;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return collect_fail("hipSetDevice", e);
+    if (abi::on_device(g_collect_err, device)) return -1;
     const EnvOut out{obs_internal, obs_external, reward, terminated, truncated, terminal_obs_internal, terminal_obs_external,
                      max_episode_steps, nullptr};
     const CollectK co{theta, buf_obs, buf_next_obs, buf_actions, buf_rewards, buf_dones, ep_return, actions, done, success,
                       episode_return, *collect};
     hipLaunchKernelGGL((env_step_kernel<false, true>), dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state,
                        (const int32_t*)nullptr, out, (int)B, EnvFresh{}, co);
-    e = hipGetLastError();
-    if (e != hipSuccess) return collect_fail("env_step_kernel launch", e);
-    return 0;
+    return abi::launched(g_collect_err, "env_step_kernel launch");
 }
 
-const char* mpcgpu_collect_last_error(void) { return envgpu::g_collect_err.c_str(); }
+const char* mpcgpu_collect_last_error(void) { return envgpu::g_collect_err.text.c_str(); }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// envgpu_internal.hpp -- what the image-observation entries (envimg.hip) share with the environment step (envgpu.hip).
+// envgpu_internal.hpp -- what the image-observation entries (envimg.hip) and the map stream (mapgpu.hip) share with the
+// environment step (envgpu.hip): the record layout, the error slot of mpcgpu_env_last_error and the shared argument checks.
 // Not part of the C-ABI: the public declarations are in include/mpcgpu_env.h.
 #pragma once
 
@@ -7,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/mpcgpu_env.h"
+#include "abi_host.hpp"
 
 namespace envgpu {
 
@@ -40,8 +42,18 @@ constexpr int IMG_STATE = 16;
 constexpr int IMG_HIST = 6;
 constexpr int IMG_PRE = 8;
 
+// what every entry that takes mpcgpu_env_params says when layout() refuses them
+constexpr const char* BAD_PARAMS = "invalid mpcgpu_env_params (P 2..64, M 0..31, K 1..4, E >= 1)";
+
 bool layout(const mpcgpu_env_params& p, EnvK& k);
-int fail(const char* what, hipError_t e = hipSuccess);
+extern thread_local abi::ErrorSlot g_err;   // mpcgpu_env_last_error: the ray, image and fresh-map entries share it
+inline int fail(const char* what) { return g_err.fail(what); }
+// the argument checks of the auto-reset step, rays and images (the refusal names the variant's entry that only observes)
+int autoreset_args(const int32_t* action, int32_t max_episode_steps, bool images);
+// the argument checks of the fresh-map step, rays and images (include/mpcgpu_map.h).  `also_bad` is a refusal of the caller's own
+// that ranks second, or NULL.  `out` comes in filled as for an auto-reset step; with max_episode_steps = 0 the step only
+// observes and the fields of the in-kernel reset are cleared
+int fresh_args(const EnvFresh& fresh, const char* also_bad, const int32_t* action, EnvOut& out);
 // validates params and pointers (obs_ext may be NULL when need_ext is false) and enqueues env_step_kernel<false>, or
 // env_step_kernel<true> on a [2][B][rec] table when `fresh` is given
 int launch_step(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records, double* state,

@@ -382,7 +382,7 @@ static int32_t launch(int32_t device, const mpcgpu_env_params* params, const mpc
                       const envgpu::EnvFresh* fresh = nullptr) {
     if (check_img(img) != 0) return -1;
     EnvK ek;
-    if (!params || !envgpu::layout(*params, ek)) return envgpu::fail("invalid mpcgpu_env_params (P 2..64, M 0..31, K 1..4, E >= 1)");
+    if (!params || !envgpu::layout(*params, ek)) return envgpu::fail(envgpu::BAD_PARAMS);
     const size_t dyn = (size_t)2 * params->n_edge_max * sizeof(EdgePix);
     if (dyn + sizeof(Shared) > (size_t)LDS_LIMIT)
         return envgpu::fail("too many outline edges for the image kernel (n_edge_max * 48 bytes + 17 KB must fit 64 KB of LDS)");
@@ -404,9 +404,7 @@ static int32_t launch(int32_t device, const mpcgpu_env_params* params, const mpc
     else
         hipLaunchKernelGGL(env_img_kernel<false>, dim3(B), dim3(THREADS), dyn, (hipStream_t)stream, k, records, state, img_state,
                            dfield, obs_image, term_image, out.pre_reset ? 1 : 0, (int)B, (const int32_t*)nullptr);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return envgpu::fail("env_img_kernel launch", e);
-    return 0;
+    return abi::launched(envgpu::g_err, "env_img_kernel launch");
 }
 
 }  // namespace envimg
@@ -434,8 +432,7 @@ int32_t mpcgpu_env_step_imgs_autoreset_dev(int32_t device, const mpcgpu_env_para
                                            double* reward, uint8_t* terminated, uint8_t* truncated,
                                            float* terminal_obs_internal, uint8_t* terminal_obs_image,
                                            int32_t max_episode_steps, void* stream) {
-    if (!action) return envgpu::fail("auto-reset needs actions (use mpcgpu_env_step_imgs_dev to observe)");
-    if (max_episode_steps <= 0) return envgpu::fail("max_episode_steps must be positive");
+    if (envgpu::autoreset_args(action, max_episode_steps, true)) return -1;
     if (!img_state) return envgpu::fail("null pointer / negative batch");
     envgpu::EnvOut out{obs_internal, nullptr, reward, terminated, truncated, terminal_obs_internal, nullptr,
                        max_episode_steps, img_state};
@@ -451,17 +448,13 @@ int32_t mpcgpu_env_step_imgs_fresh_dev(int32_t device, const mpcgpu_env_params* 
                                        uint8_t* obs_image, double* reward, uint8_t* terminated, uint8_t* truncated,
                                        float* terminal_obs_internal, uint8_t* terminal_obs_image,
                                        int32_t max_episode_steps, void* stream) {
-    if (!which || !spare_ready || !loaded || !stale) return envgpu::fail("null pointer (which / spare_ready / loaded / stale)");
-    if (!img_state || !distance_field || !obs_image) return envgpu::fail("null pointer (img_state / distance_field / obs_image)");
-    if (max_episode_steps < 0) return envgpu::fail("max_episode_steps must not be negative");
-    if (max_episode_steps > 0 && !action) return envgpu::fail("auto-reset needs actions (max_episode_steps = 0 observes)");
-    if (max_episode_steps > 0 && !truncated) return envgpu::fail("null pointer (truncated)");
-    const bool reset = max_episode_steps > 0;
-    envgpu::EnvOut out{obs_internal, nullptr, reward, terminated, reset ? truncated : nullptr,
-                       reset ? terminal_obs_internal : nullptr, nullptr, max_episode_steps, reset ? img_state : nullptr};
+    envgpu::EnvOut out{obs_internal, nullptr, reward, terminated, truncated, terminal_obs_internal, nullptr, max_episode_steps,
+                       img_state};
     const envgpu::EnvFresh fresh{which, spare_ready, loaded, stale};
+    const bool mine = img_state && distance_field && obs_image;
+    if (envgpu::fresh_args(fresh, mine ? nullptr : "null pointer (img_state / distance_field / obs_image)", action, out)) return -1;
     return envimg::launch(device, params, img, B, records2, state, img_state, distance_field, action, out, obs_image,
-                          reset ? terminal_obs_image : nullptr, stream, &fresh);
+                          max_episode_steps > 0 ? terminal_obs_image : nullptr, stream, &fresh);
 }
 
 }  // extern "C"

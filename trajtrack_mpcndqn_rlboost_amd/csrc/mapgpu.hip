@@ -13,8 +13,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "../../include/mpcgpu_map.h"
 #include "counter_stream.hpp"
@@ -411,14 +409,8 @@ __global__ __launch_bounds__(WAVE) void map_record_kernel(envgpu::EnvK k, const 
     }
 }
 
-thread_local std::string g_err;
-int fail(const char* what, hipError_t e = hipSuccess) {
-    char buf[256];
-    if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    else snprintf(buf, sizeof buf, "%s", what);
-    g_err = buf;
-    return -1;
-}
+thread_local abi::ErrorSlot g_err;
+int fail(const char* what) { return g_err.fail(what); }
 
 }  // namespace mapgpu
 
@@ -430,46 +422,37 @@ int32_t mpcgpu_map_draw_dev(int32_t device, int32_t B, uint64_t seed, double* sp
                             int32_t* attempt, void* stream) {
     if (B < 0 || !spec_table || !spare_ready || !attempt) return mapgpu::fail("null pointer / negative batch");
     if (B == 0) return 0;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return mapgpu::fail("hipSetDevice", e);
+    if (abi::on_device(mapgpu::g_err, device)) return -1;
     hipLaunchKernelGGL(mapgpu::map_draw_kernel, dim3(B), dim3(mapgpu::WAVE), 0, (hipStream_t)stream, seed, spec_table,
                        spare_ready, attempt, (int)B);
-    e = hipGetLastError();
-    if (e != hipSuccess) return mapgpu::fail("map_draw_kernel launch", e);
-    return 0;
+    return abi::launched(mapgpu::g_err, "map_draw_kernel launch");
 }
 
 int32_t mpcgpu_map_rings_dev(int32_t device, int32_t B, const double* spec_table, const int32_t* spare_ready, double* rings,
                              double* start_goal, void* stream) {
     if (B < 0 || !spec_table || !spare_ready || !rings || !start_goal) return mapgpu::fail("null pointer / negative batch");
     if (B == 0) return 0;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return mapgpu::fail("hipSetDevice", e);
+    if (abi::on_device(mapgpu::g_err, device)) return -1;
     hipLaunchKernelGGL(mapgpu::map_rings_kernel, dim3(B), dim3(mapgpu::WAVE), 0, (hipStream_t)stream, spec_table, spare_ready,
                        rings, start_goal, (int)B);
-    e = hipGetLastError();
-    if (e != hipSuccess) return mapgpu::fail("map_rings_kernel launch", e);
-    return 0;
+    return abi::launched(mapgpu::g_err, "map_rings_kernel launch");
 }
 
 int32_t mpcgpu_map_record_dev(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* spec_table,
                               const int32_t* plan_status, const int32_t* plan_n_nodes, const double* plan_nodes, double* records2,
                               const int32_t* which, int32_t* spare_ready, int32_t* status, void* stream) {
     envgpu::EnvK k;
-    if (!params || !envgpu::layout(*params, k)) return mapgpu::fail("invalid mpcgpu_env_params (P 2..64, M 0..31, K 1..4, E >= 1)");
+    if (!params || !envgpu::layout(*params, k)) return mapgpu::fail(envgpu::BAD_PARAMS);
     if (B < 0 || !spec_table || !plan_status || !plan_n_nodes || !plan_nodes || !records2 || !which || !spare_ready || !status)
         return mapgpu::fail("null pointer / negative batch");
     if (k.o_edge > mapgpu::HEAD_CAP) return mapgpu::fail("record header larger than the kernel stages");
     if (B == 0) return 0;
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return mapgpu::fail("hipSetDevice", e);
+    if (abi::on_device(mapgpu::g_err, device)) return -1;
     hipLaunchKernelGGL(mapgpu::map_record_kernel, dim3(B), dim3(mapgpu::WAVE), 0, (hipStream_t)stream, k, spec_table, plan_status,
                        plan_n_nodes, plan_nodes, records2, which, spare_ready, status, (int)B);
-    e = hipGetLastError();
-    if (e != hipSuccess) return mapgpu::fail("map_record_kernel launch", e);
-    return 0;
+    return abi::launched(mapgpu::g_err, "map_record_kernel launch");
 }
 
-const char* mpcgpu_map_last_error(void) { return mapgpu::g_err.c_str(); }
+const char* mpcgpu_map_last_error(void) { return mapgpu::g_err.text.c_str(); }
 
 }  // extern "C"

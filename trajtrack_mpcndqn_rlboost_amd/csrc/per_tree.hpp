@@ -23,6 +23,9 @@ __device__ inline double pow_as_libm(double x, double y) {
 
 __host__ __device__ inline int depth_of(int64_t i) { return 63 - __builtin_clzll((unsigned long long)(i + 1)); }
 
+// what every entry that takes mpcgpu_per_params says when valid() refuses them
+constexpr const char* BAD_PARAMS =
+    "invalid mpcgpu_per_params (capacity 1..2^30, update_max_freq >= 1, alpha, epsilon >= 0, 0 <= beta < inf, initial_priority > 0)";
 inline bool valid(const mpcgpu_per_params* p) {
     return p && p->capacity >= 1 && p->capacity <= ((int64_t)1 << 30) && p->update_max_freq >= 1 && p->alpha >= 0.0 &&
            p->beta >= 0.0 && p->beta <= DBL_MAX && p->epsilon >= 0.0 && p->initial_priority > 0.0;      // a NaN fails every comparison

@@ -16,10 +16,9 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "../../include/mpcgpu_per.h"
+#include "abi_host.hpp"
 #include "per_tree.hpp"
 
 namespace pergpu {
@@ -193,25 +192,14 @@ __global__ void per_stats_kernel(const double* tree, const double* state, double
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-thread_local std::string g_err;
-int fail(const char* what, hipError_t e = hipSuccess) {
-    char buf[256];
-    if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    else snprintf(buf, sizeof buf, "%s", what);
-    g_err = buf;
-    return -1;
-}
+thread_local abi::ErrorSlot g_err;
+int fail(const char* what) { return g_err.fail(what); }
+int launched(const char* what) { return abi::launched(g_err, what); }
 
+// the device is set BEFORE the entries check their pointers: a caller without a device hears of that first
 int begin(int32_t device, const mpcgpu_per_params* p) {
-    if (!valid(p)) return fail("invalid mpcgpu_per_params (capacity 1..2^30, update_max_freq >= 1, alpha, epsilon >= 0, 0 <= beta < inf, initial_priority > 0)");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail("hipSetDevice", e);
-    return 0;
-}
-
-int launched(const char* what) {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(what, e);
+    if (!valid(p)) return fail(BAD_PARAMS);
+    return abi::on_device(g_err, device);
 }
 
 // the leaves of ring rows pos .. pos + rows - 1 (mod C) as ranges of tree indices, each on one depth
@@ -312,6 +300,6 @@ int32_t mpcgpu_per_stats_dev(int32_t device, const mpcgpu_per_params* params, co
     return launched("per_stats_kernel launch");
 }
 
-const char* mpcgpu_per_last_error(void) { return pergpu::g_err.c_str(); }
+const char* mpcgpu_per_last_error(void) { return pergpu::g_err.text.c_str(); }
 
 }  // extern "C"

@@ -14,10 +14,9 @@
 #include <climits>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "../../include/mpcgpu_plan.h"
+#include "abi_host.hpp"
 
 namespace plangpu {
 
@@ -288,14 +287,8 @@ __global__ void __launch_bounds__(THREADS) plan_paths_kernel(mpcgpu_plan_params 
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-thread_local std::string g_err;
-int fail(const char* what, hipError_t e = hipSuccess) {
-    char buf[256];
-    if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    else snprintf(buf, sizeof buf, "%s", what);
-    g_err = buf;
-    return -1;
-}
+thread_local abi::ErrorSlot g_err;
+int fail(const char* what) { return g_err.fail(what); }
 
 int check(const mpcgpu_plan_params* p) {
     if (!p) return fail("null mpcgpu_plan_params");
@@ -326,14 +319,12 @@ int32_t mpcgpu_plan_paths_dev(int32_t device, const mpcgpu_plan_params* params, 
     if (check(params)) return -1;
     if (B < 1) return fail("plan: B >= 1");
     if (!rings || !start_goal || !status || !n_nodes || !nodes || !length) return fail("null pointer");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail("hipSetDevice", e);
+    if (abi::on_device(g_err, device)) return -1;
     hipLaunchKernelGGL(plan_paths_kernel, dim3((unsigned)B), dim3(THREADS), 0, (hipStream_t)stream, *params, record_doubles(params), rings,
                        start_goal, status, n_nodes, nodes, length);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail("plan_paths_kernel launch", e);
+    return abi::launched(g_err, "plan_paths_kernel launch");
 }
 
-const char* mpcgpu_plan_last_error(void) { return plangpu::g_err.c_str(); }
+const char* mpcgpu_plan_last_error(void) { return plangpu::g_err.text.c_str(); }
 
 }  // extern "C"

@@ -62,15 +62,6 @@ class _CConfig(C.Structure):
     ]
 
 
-EXPORTS = ("mpcgpu_abi_version", "mpcgpu_create", "mpcgpu_destroy", "mpcgpu_last_error", "mpcgpu_num_params",
-           "mpcgpu_solve_batch", "mpcgpu_solve_batch_dev", "mpcgpu_cost_grad_batch", "mpcgpu_psi_value_batch", "mpcgpu_last_timing",
-           "mpcgpu_last_eval_counts", "mpcgpu_last_shape", "mpcgpu_last_waves_per_simd", "mpcgpu_reserve_shape",
-           "mpcgpu_set_option", "mpcgpu_last_problems_per_wavefront", "mpcgpu_last_ordered", "mpcgpu_last_tail_promotion", "mpcgpu_last_tail_timeouts", "mpcgpu_last_tail_timing", "mpcgpu_last_latency_kernel", "mpcgpu_reserve_batch", "mpcgpu_last_table_kind", "mpcgpu_tracker_window_dev",
-           "mpcgpu_tracker_step_dev", "mpcgpu_rl_reference_dev", "mpcgpu_hint_switch_dev", "mpcgpu_debug_read_workspace",
-           "mpcgpu_workspace_stride", "mpcgpu_workspace_record", "mpcgpu_debug_prep", "mpcgpu_debug_tracker_assemble",
-           "mpcgpu_debug_lbfgs_direction")
-
-
 def library_path() -> str:
     return _LIB
 
@@ -93,6 +84,53 @@ class CTracker(C.Structure):
                 ("tuning", C.c_double * 10), ("base_speed", C.c_double), ("low_speed", C.c_double),
                 ("stc_weight", C.c_double), ("dyn_weight", C.c_double)]
 
+
+_I32, _DP, _IP, _VP, _TP = C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p, C.POINTER(CTracker)
+# export -> (restype, argtypes): every declaration of include/mpcgpu.h
+_CORE_TABLE = {
+    "mpcgpu_abi_version": (_I32, []),
+    "mpcgpu_create": (_I32, [C.POINTER(_CConfig), C.POINTER(_VP)]),
+    "mpcgpu_destroy": (None, [_VP]),
+    "mpcgpu_last_error": (C.c_char_p, [_VP]),
+    "mpcgpu_num_params": (_I32, [_VP]),
+    "mpcgpu_solve_batch": (_I32, [_VP, _I32] + [_DP] * 6 + [_IP] * 3 + [_DP] * 4),
+    "mpcgpu_solve_batch_dev": (_I32, [_VP, _I32] + [_VP] * 13 + [_VP]),
+    "mpcgpu_cost_grad_batch": (_I32, [_VP, _I32] + [_DP] * 8),
+    "mpcgpu_psi_value_batch": (_I32, [_VP, _I32] + [_DP] * 4),
+    "mpcgpu_last_timing": (_I32, [_VP, _DP, _DP]),
+    "mpcgpu_last_eval_counts": (_I32, [_VP, _I32, _IP, _IP, _VP]),
+    "mpcgpu_last_shape": (_I32, [_VP, _IP, _IP, _IP, _IP]),
+    "mpcgpu_last_waves_per_simd": (_I32, [_VP]),
+    "mpcgpu_reserve_shape": (_I32, [_VP, _I32, _I32, _I32, _I32]),
+    "mpcgpu_set_option": (_I32, [_VP, _I32, C.c_double]),
+    "mpcgpu_last_problems_per_wavefront": (_I32, [_VP]),
+    "mpcgpu_last_ordered": (_I32, [_VP]),
+    "mpcgpu_last_tail_promotion": (_I32, [_VP, _IP, _VP]),
+    "mpcgpu_last_tail_timeouts": (_I32, [_VP, _IP, _VP]),
+    "mpcgpu_last_tail_timing": (_I32, [_VP, _DP, _DP]),
+    "mpcgpu_last_latency_kernel": (_I32, [_VP]),
+    "mpcgpu_reserve_batch": (_I32, [_VP, _I32]),
+    "mpcgpu_last_table_kind": (_I32, [_VP]),
+    "mpcgpu_tracker_window_dev": (_I32, [_VP, _TP, _VP, _VP]),
+    "mpcgpu_tracker_step_dev": (_I32, [_VP, _TP] + [_VP] * 8 + [_VP]),
+    "mpcgpu_rl_reference_dev": (_I32, [_VP, _I32, _VP, _I32, _VP, C.c_double, _I32, C.c_double, _DP, _VP, _VP]),
+    "mpcgpu_hint_switch_dev": (_I32, [_VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP,
+                                      C.c_double, C.c_double, C.c_double, _VP, _VP, _VP, _VP]),
+    "mpcgpu_debug_read_workspace": (_I32, [_VP, _I32, _DP]),
+    "mpcgpu_workspace_stride": (_I32, [_VP]),
+    "mpcgpu_workspace_record": (_I32, [_VP]),
+    "mpcgpu_debug_prep": (_I32, [_VP, _I32, _DP]),
+    "mpcgpu_debug_tracker_assemble": (_I32, [_VP, _TP, _VP]),
+    "mpcgpu_debug_lbfgs_direction": (_I32, [_VP, _I32, _I32, _DP, _DP, _DP, _DP, _IP]),
+}
+EXPORTS = tuple(_CORE_TABLE)
+# absent only in an older build loaded for an A/B run (MPCGPU_ALLOW_ABI)
+_CORE_OPTIONAL = ("mpcgpu_psi_value_batch", "mpcgpu_last_tail_promotion", "mpcgpu_last_tail_timeouts", "mpcgpu_last_tail_timing")
+# -DMPC_TRACE builds only (tests); not declared in the header
+_TRACE_TABLE = {
+    "mpcgpu_debug_set_trace": (_I32, [_VP, _I32]),
+    "mpcgpu_debug_read_trace": (_I32, [_VP, _I32, _DP]),
+}
 
 _libs = {}
 
@@ -121,101 +159,35 @@ def load_library(path: Optional[str] = None):
         raise MpcGpuError(f"{_LIB} not found: build it with `make -C {os.path.join(_PKG, 'csrc')}` "
                           "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     L = C.CDLL(_LIB)
-    dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p
-    L.mpcgpu_abi_version.restype = C.c_int32
-    L.mpcgpu_create.argtypes = [C.POINTER(_CConfig), C.POINTER(vp)]
-    L.mpcgpu_create.restype = C.c_int32
-    L.mpcgpu_destroy.argtypes = [vp]
-    L.mpcgpu_destroy.restype = None
-    L.mpcgpu_last_error.argtypes = [vp]
-    L.mpcgpu_last_error.restype = C.c_char_p
-    L.mpcgpu_num_params.argtypes = [vp]
-    L.mpcgpu_num_params.restype = C.c_int32
-    L.mpcgpu_solve_batch.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, dp, ip, ip, ip, dp, dp, dp, dp]
-    L.mpcgpu_solve_batch.restype = C.c_int32
-    L.mpcgpu_solve_batch_dev.argtypes = [vp, C.c_int32] + [vp] * 13 + [vp]
-    L.mpcgpu_solve_batch_dev.restype = C.c_int32
-    L.mpcgpu_cost_grad_batch.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp]
-    L.mpcgpu_cost_grad_batch.restype = C.c_int32
-    if hasattr(L, "mpcgpu_psi_value_batch"):   # (absent only in an older build loaded for an A/B run)
-        L.mpcgpu_psi_value_batch.argtypes = [vp, C.c_int32, dp, dp, dp, dp]
-        L.mpcgpu_psi_value_batch.restype = C.c_int32
-    L.mpcgpu_last_timing.argtypes = [vp, dp, dp]
-    L.mpcgpu_last_timing.restype = C.c_int32
-    L.mpcgpu_last_eval_counts.argtypes = [vp, C.c_int32, ip, ip, vp]
-    L.mpcgpu_last_eval_counts.restype = C.c_int32
-    L.mpcgpu_last_shape.argtypes = [vp, ip, ip, ip, ip]
-    L.mpcgpu_last_shape.restype = C.c_int32
-    L.mpcgpu_last_waves_per_simd.argtypes = [vp]
-    L.mpcgpu_last_waves_per_simd.restype = C.c_int32
-    L.mpcgpu_last_latency_kernel.argtypes = [vp]
-    L.mpcgpu_last_latency_kernel.restype = C.c_int32
-    L.mpcgpu_last_problems_per_wavefront.argtypes = [vp]
-    L.mpcgpu_last_problems_per_wavefront.restype = C.c_int32
-    L.mpcgpu_last_ordered.argtypes = [vp]
-    L.mpcgpu_last_ordered.restype = C.c_int32
-    if hasattr(L, "mpcgpu_last_tail_timeouts"):
-        L.mpcgpu_last_tail_timeouts.argtypes = [vp, ip, vp]
-        L.mpcgpu_last_tail_timeouts.restype = C.c_int32
-    if hasattr(L, "mpcgpu_last_tail_promotion"):   # (absent only in an old build loaded for an A/B run, see MPCGPU_ALLOW_ABI)
-        L.mpcgpu_last_tail_promotion.argtypes = [vp, ip, vp]
-        L.mpcgpu_last_tail_promotion.restype = C.c_int32
-        L.mpcgpu_last_tail_timing.argtypes = [vp, dp, dp]
-        L.mpcgpu_last_tail_timing.restype = C.c_int32
-    L.mpcgpu_reserve_shape.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    L.mpcgpu_reserve_shape.restype = C.c_int32
-    tp = C.POINTER(CTracker)
-    L.mpcgpu_tracker_window_dev.argtypes = [vp, tp, vp, vp]
-    L.mpcgpu_tracker_window_dev.restype = C.c_int32
-    L.mpcgpu_tracker_step_dev.argtypes = [vp, tp] + [vp] * 8 + [vp]
-    L.mpcgpu_tracker_step_dev.restype = C.c_int32
-    L.mpcgpu_rl_reference_dev.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_double, C.c_int32, C.c_double, dp, vp, vp]
-    L.mpcgpu_rl_reference_dev.restype = C.c_int32
-    L.mpcgpu_hint_switch_dev.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32, vp,
-                                         C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
-    L.mpcgpu_hint_switch_dev.restype = C.c_int32
-    L.mpcgpu_debug_read_workspace.argtypes = [vp, C.c_int32, dp]
-    L.mpcgpu_debug_read_workspace.restype = C.c_int32
-    L.mpcgpu_workspace_stride.argtypes = [vp]
-    L.mpcgpu_workspace_stride.restype = C.c_int32
-    L.mpcgpu_workspace_record.argtypes = [vp]
-    L.mpcgpu_workspace_record.restype = C.c_int32
-    L.mpcgpu_debug_prep.argtypes = [vp, C.c_int32, dp]
-    L.mpcgpu_debug_prep.restype = C.c_int32
-    L.mpcgpu_debug_tracker_assemble.argtypes = [vp, tp, vp]
-    L.mpcgpu_debug_tracker_assemble.restype = C.c_int32
-    L.mpcgpu_debug_lbfgs_direction.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, ip]
-    L.mpcgpu_debug_lbfgs_direction.restype = C.c_int32
-    L.mpcgpu_last_table_kind.argtypes = [vp]
-    L.mpcgpu_last_table_kind.restype = C.c_int32
-    L.mpcgpu_reserve_batch.argtypes = [vp, C.c_int32]
-    L.mpcgpu_reserve_batch.restype = C.c_int32
-    L.mpcgpu_set_option.argtypes = [vp, C.c_int32, C.c_double]
-    L.mpcgpu_set_option.restype = C.c_int32
+    _bind(L)
     if L.mpcgpu_abi_version() != ABI_VERSION and not os.environ.get("MPCGPU_ALLOW_ABI"):   # (A/B runs against an older build)
         raise MpcGpuError(f"{_LIB} has ABI version {L.mpcgpu_abi_version()}, this binding needs {ABI_VERSION}: rebuild it")
-    if hasattr(L, "mpcgpu_debug_set_trace"):     # -DMPC_TRACE builds (tests)
-        L.mpcgpu_debug_set_trace.argtypes = [vp, C.c_int32]
-        L.mpcgpu_debug_set_trace.restype = C.c_int32
-        L.mpcgpu_debug_read_trace.argtypes = [vp, C.c_int32, dp]
-        L.mpcgpu_debug_read_trace.restype = C.c_int32
     _libs[_LIB] = L
     return L
 
 
-def bind_exports(lib, tag: str, table, sources: str):
-    """Signatures of a side module's exports (environment, map stream, planner, replay tree, fleet) on the handle ``lib``:
-    ``table`` is ``{export name: (restype, argtypes)}``, ``sources`` the files to rebuild when an export is missing.  Done
-    once per handle and ``tag``; returns ``lib``."""
+def _bind(lib):
+    bind_exports(lib, "core", _CORE_TABLE, "csrc/mpcgpu.hip", optional=_CORE_OPTIONAL)
+    return bind_exports(lib, "trace", _TRACE_TABLE, "csrc/mpcgpu.hip", optional=tuple(_TRACE_TABLE))
+
+
+def bind_exports(lib, tag: str, table, sources: str, optional=()):
+    """Signatures of the exports of the core library or of a side module (environment, map stream, planner, replay tree,
+    fleet) on the handle ``lib``: ``table`` is ``{export name: (restype, argtypes)}``, ``sources`` the files to rebuild when an
+    export is missing; an export named in ``optional`` is bound where the library has it.  Done once per handle and ``tag``;
+    returns ``lib``."""
     bound = getattr(lib, "_bound_tags", None)
     if bound is None:
         bound = lib._bound_tags = set()
     if tag in bound:
         return lib
-    missing = [name for name in table if not hasattr(lib, name)]
+    absent = [name for name in table if not hasattr(lib, name)]
+    missing = [name for name in absent if name not in optional]
     if missing:
         raise MpcGpuError(f"libmpcgpu.so lacks {missing}: rebuild it ({sources}); there is no fallback")
     for name, (restype, argtypes) in table.items():
+        if name in absent:
+            continue
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     bound.add(tag)
