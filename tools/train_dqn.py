@@ -4,7 +4,7 @@
     python tools/train_dqn.py [--gpus N] [--envs 4096] [--timesteps 4000000] [--gradient-steps 16] [--batch-size 256]
                               [--save DIR] [--resume DIR/checkpoint.pt] [--checkpoint-every STEPS]
                               [--images] [--fresh-maps] [--per] [--buffer-size N] [--graph | --fused [--per-in-kernel]]
-                              [--collect-in-kernel]
+                              [--collect-in-kernel | --fresh-maps --collect-turnover]
 
 `--images` trains dqn.ImageQNetwork on the image environment (rl_env.BatchedImgsEnv); with `--fresh-maps` every episode of it
 starts on a new random map too (map_turnover=True, capacity map_stream.DYNAMIC_CAPACITY, stream seed + rank).
@@ -17,6 +17,10 @@ tree's kernels unless `--per-in-kernel` moves sample, update and
 `--collect-in-kernel` (ray environment without --fresh-maps, one or several GPUs) collects the steps of a round -- act, auto-reset
 step, buffer rows, episode returns -- inside ONE launch of the step kernel (collect.collect_rays) instead of some
 forty launches per step; exploration then draws from a counter stream of its own.
+
+`--fresh-maps --collect-turnover` (ray environment) does the same on the two-record table of the map stream
+(collect_fresh.collect_rays_fresh): a row whose episode ends inside a launch moves to its new map there; the
+refill of the spares follows a launch, never splits it.
 
 `--save DIR` writes what the reference's run leaves behind (src/test_block_rl.py:73-76,89-96: EvalCallback's best_model and
 model.save's final_model) -- best_model.pt whenever the mean return of a progress window improves, final_model.pt at the end --
@@ -104,6 +108,8 @@ def parse_args(argv=None):
                     help="with --fused --per on one GPU: sample, update and re-prioritise inside the launch, one launch per update round")
     ap.add_argument("--collect-in-kernel", action="store_true",
                     help="collect the steps of a round inside one launch of the step kernel (ray environment, not with --fresh-maps)")
+    ap.add_argument("--collect-turnover", action="store_true",
+                    help="with --fresh-maps (ray environment): collect inside the launch on the two-record table of the map stream")
     ap.add_argument("--save", default=None, help="directory for best_model.pt / final_model.pt / checkpoint.pt")
     ap.add_argument("--resume", default=None, help="checkpoint.pt of an earlier run with the same arguments")
     ap.add_argument("--checkpoint-every", type=int, default=0, help="environment steps between checkpoints (0: only at the end)")
@@ -120,7 +126,11 @@ def parse_args(argv=None):
     if args.per_in_kernel and args.gpus > 1:
         ap.error("--per-in-kernel is the one-GPU path: several ranks update step by step around the all-reduce")
     if args.collect_in_kernel and (args.images or args.fresh_maps):
-        ap.error("--collect-in-kernel is built for the ray environment on one record table: not with --images or --fresh-maps")
+        ap.error("--collect-in-kernel is built for the ray environment on one record table: not with --images or --fresh-maps "
+                 "(--fresh-maps --collect-turnover collects inside the launch on the two-record table)")
+    if args.collect_turnover and (args.images or not args.fresh_maps):
+        ap.error("--collect-turnover is collection inside the launch on the two-record table: it needs --fresh-maps and the ray "
+                 "environment (not --images)")
     return args
 
 
@@ -156,7 +166,8 @@ def main():
                                    batch_size=args.batch_size, train_freq=4, gradient_steps=args.gradient_steps,
                                    target_update_interval=200_000, exploration_fraction=0.3, use_graph=args.graph,
                                    track_episodes=False, per=args.per, fused=args.fused, per_in_kernel=args.per_in_kernel,
-                                   collect_in_kernel=args.collect_in_kernel)
+                                   collect_in_kernel=args.collect_in_kernel or args.collect_turnover,
+                                   collect_turnover=args.collect_turnover)
     ck_name = "checkpoint.pt" if rank == 0 else f"checkpoint.rank{rank}.pt"
     if args.resume:
         learner.load(args.resume if rank == 0 else os.path.join(os.path.dirname(args.resume), ck_name))
@@ -211,6 +222,7 @@ def main():
                                      "batch_size": args.batch_size, "gradient_steps": args.gradient_steps, "double_q": bool(args.double_q),
                                      "per": bool(args.per), "images": bool(args.images), "fresh_maps": bool(args.fresh_maps),
                                      "collect_in_kernel": bool(args.collect_in_kernel),
+                                     "collect_turnover": bool(args.collect_turnover),
                                      "buffer_size": buffer_size},
                           "success_rate": stats["success_rate"], "mean_return": stats["mean_return"]}))
     if world > 1:

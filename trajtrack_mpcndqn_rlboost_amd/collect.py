@@ -95,18 +95,10 @@ def act(env_or_obs, theta: torch.Tensor, eps: float, seed: int, serial: int, ret
     return (actions, q) if return_q else actions
 
 
-def collect_rays(env, theta: torch.Tensor, buffer, eps: Sequence[float], seed: int, serial: int, ep_return: torch.Tensor,
-                 out: Optional[Dict[str, torch.Tensor]] = None) -> None:
-    """``len(eps)`` steps (1 .. 64) of ``env`` in ONE launch: step t acts on the observation the environment holds with
-    ``eps[t]`` and the counter stream ``(seed, serial + t)``, steps with auto-reset and writes its B transitions into
-    ``buffer`` (a uniform or prioritized ``dqn_train.ReplayBuffer`` of flat observations) from ``buffer.pos`` on.
-    ``ep_return`` [B] float64 is the running return per row, updated in place.  ``out`` may hold ``[T, B]`` tensors
-    ``actions`` (int32), ``done``, ``success`` (uint8) and ``episode_return`` (float64, written where ``done``).
-
-    ``buffer.pos`` and ``buffer.size`` move on as T calls of ``add`` would move them; with a sum tree those T calls of
-    ``sum_tree.add`` follow the launch, one per step and in order (the tree's add counter and its maximum depend on the
-    number of calls).  Refusals come before anything is enqueued and leave every tensor as it was."""
-    check_env(env)
+def rays_args(env, theta: torch.Tensor, buffer, eps: Sequence[float], seed: int, serial: int, ep_return: torch.Tensor,
+              out: Optional[Dict[str, torch.Tensor]]) -> tuple:
+    """The argument checks the T-step entries share (:func:`collect_rays`, ``collect_fresh.collect_rays_fresh``) -> the
+    arguments of either entry from ``state`` on, the stream included.  ``ValueError`` before anything is enqueued."""
     T, B = len(eps), env.B
     device = env.device
     theta = _theta(theta, device)
@@ -123,15 +115,37 @@ def collect_rays(env, theta: torch.Tensor, buffer, eps: Sequence[float], seed: i
                         pos0=int(buffer.pos), T=T if T <= MAX_STEPS else MAX_STEPS + 1)
     for t, e in enumerate(eps[:MAX_STEPS]):
         p.eps[t] = float(e)
-    lib = _bind(env._lib)
-    _check(lib, lib.mpcgpu_collect_rays_dev(
-        env.device_index, C.byref(env.params), B, env.records.data_ptr(), env.state.data_ptr(), env.obs_internal.data_ptr(),
-        env.obs_external.data_ptr(), env.reward.data_ptr(), env.terminated.data_ptr(), env.truncated.data_ptr(),
-        env.term_internal.data_ptr(), env.term_external.data_ptr(), int(env.max_episode_steps), theta.data_ptr(), C.byref(p),
-        buffer.obs.data_ptr(), buffer.next_obs.data_ptr(), buffer.actions.data_ptr(), buffer.rewards.data_ptr(),
-        buffer.dones.data_ptr(), ep_return.data_ptr(), ptr["actions"], ptr["done"], ptr["success"], ptr["episode_return"],
-        torch.cuda.current_stream(device).cuda_stream))
+    return (env.state.data_ptr(), env.obs_internal.data_ptr(),
+            env.obs_external.data_ptr(), env.reward.data_ptr(), env.terminated.data_ptr(), env.truncated.data_ptr(),
+            env.term_internal.data_ptr(), env.term_external.data_ptr(), int(env.max_episode_steps), theta.data_ptr(), C.byref(p),
+            buffer.obs.data_ptr(), buffer.next_obs.data_ptr(), buffer.actions.data_ptr(), buffer.rewards.data_ptr(),
+            buffer.dones.data_ptr(), ep_return.data_ptr(), ptr["actions"], ptr["done"], ptr["success"], ptr["episode_return"],
+            torch.cuda.current_stream(device).cuda_stream)
+
+
+def ring_moved(buffer, T: int, B: int) -> None:
+    """Behind a launch of T steps: ``buffer.pos`` and ``buffer.size`` as T calls of ``add`` move them, and with a sum tree its
+    T calls of ``add``, one per step and in order."""
     for _ in range(T):
         if buffer.sum_tree is not None:
             buffer.sum_tree.add(buffer.pos, B, buffer.size)      # the new rows take the running maximum priority
         buffer.pos, buffer.size = (buffer.pos + B) % buffer.capacity, min(buffer.size + B, buffer.capacity)
+
+
+def collect_rays(env, theta: torch.Tensor, buffer, eps: Sequence[float], seed: int, serial: int, ep_return: torch.Tensor,
+                 out: Optional[Dict[str, torch.Tensor]] = None) -> None:
+    """``len(eps)`` steps (1 .. 64) of ``env`` in ONE launch: step t acts on the observation the environment holds with
+    ``eps[t]`` and the counter stream ``(seed, serial + t)``, steps with auto-reset and writes its B transitions into
+    ``buffer`` (a uniform or prioritized ``dqn_train.ReplayBuffer`` of flat observations) from ``buffer.pos`` on.
+    ``ep_return`` [B] float64 is the running return per row, updated in place.  ``out`` may hold ``[T, B]`` tensors
+    ``actions`` (int32), ``done``, ``success`` (uint8) and ``episode_return`` (float64, written where ``done``).
+
+    ``buffer.pos`` and ``buffer.size`` move on as T calls of ``add`` would move them; with a sum tree those T calls of
+    ``sum_tree.add`` follow the launch, one per step and in order (the tree's add counter and its maximum depend on the
+    number of calls).  Refusals come before anything is enqueued and leave every tensor as it was.  An environment after
+    ``enable_spares()`` is refused here: ``collect_fresh.collect_rays_fresh`` is its entry."""
+    check_env(env)
+    args = rays_args(env, theta, buffer, eps, seed, serial, ep_return, out)
+    lib = _bind(env._lib)
+    _check(lib, lib.mpcgpu_collect_rays_dev(env.device_index, C.byref(env.params), env.B, env.records.data_ptr(), *args))
+    ring_moved(buffer, len(eps), env.B)

@@ -11,8 +11,7 @@
 #include <cstdint>
 #include <type_traits>
 
-#include "../../include/mpcgpu_collect.h"
-#include "../../include/mpcgpu_map.h"
+#include "../../include/mpcgpu_collect_fresh.h"
 #include "dqn_act.hpp"
 #include "envgpu_internal.hpp"
 
@@ -124,11 +123,15 @@ __device__ __forceinline__ dqnact::ActLds& collect_lds() {   // LDS of the insta
 // the observation the previous step left in global memory, after it the transition goes into the ring.  Every trip reads the
 // state and writes it back exactly as a launch of its own does, so T trips are T launches; everything COLLECT adds sits under
 // `if constexpr`, and without it the loop is `do { } while (false)`.
+// FRESH and COLLECT (include/mpcgpu_collect_fresh.h): rec, n_path, n_obst, n_edge, gx and gy are carried from trip to trip and change
+// in the turnover block alone, which reads which[b] and spare_ready[b] from global memory in every trip -- lane 0 may have rewritten
+// them in an earlier trip of this launch; the workgroup fence and the barrier in front of the ring stores stand between that store and
+// these reads.  One spare per row: the first ending of a row in a launch takes it, every later one resets on the map the row is on
+// and counts stale[b], as T launches without a refill between them do.
 template <bool FRESH, bool COLLECT = false>
 __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double* __restrict__ rec_all, double* state_all,
                                                         const int32_t* __restrict__ action, EnvOut out, int B, EnvFresh fr,
                                                         std::conditional_t<COLLECT, CollectK, NoCollect> co) {
-    static_assert(!(FRESH && COLLECT), "collection on the two-record table is not built");
     float* const obs_int = out.obs_int;
     float* const obs_ext = out.obs_ext;
     double* const reward = out.reward;
@@ -600,6 +603,43 @@ thread_local abi::ErrorSlot g_collect_err;   // mpcgpu_collect_last_error
 int collect_fail(const char* what) { return g_collect_err.fail(what); }
 bool eps_ok(double eps) { return eps >= 0.0 && eps <= 1.0; }   // false for NaN
 
+// the argument checks and the launch of the two T-step entries: mpcgpu_collect_rays_dev (fresh = NULL, records [B][rec]) and
+// mpcgpu_collect_rays_fresh_dev (records [2][B][rec]), each with the error slot of its own.  `co` comes in without its params
+int launch_collect(abi::ErrorSlot& err, int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records,
+                   double* state, const EnvOut& out, CollectK co, const mpcgpu_collect_params* collect, void* stream,
+                   const EnvFresh* fresh) {
+    if (fresh && (!fresh->which || !fresh->spare_ready || !fresh->loaded || !fresh->stale))
+        return err.fail("null pointer (which / spare_ready / loaded / stale)");
+    EnvK k;
+    if (const char* bad = params_error(params, k)) return err.fail(bad);
+    if (!records || !state || !out.obs_int || !out.obs_ext || !out.reward || !out.terminated || !out.truncated || !out.term_int ||
+        !out.term_ext)
+        return err.fail("null pointer (an environment tensor)");
+    if (!co.theta || !collect || !co.buf_obs || !co.buf_next_obs || !co.buf_actions || !co.buf_rewards || !co.buf_dones ||
+        !co.ep_return)
+        return err.fail("null pointer (theta / collect / ring / ep_return)");
+    if (B < 0) return err.fail("negative batch");
+    if (out.max_steps <= 0) return err.fail("max_episode_steps must be positive");
+    if (collect->T < 1 || collect->T > MPCGPU_COLLECT_MAX_STEPS) return err.fail("1 <= T <= 64 (MPCGPU_COLLECT_MAX_STEPS)");
+    if (collect->capacity < 1 || collect->pos0 < 0 || collect->pos0 >= collect->capacity)
+        return err.fail("capacity >= 1 and 0 <= pos0 < capacity");
+    if ((int64_t)collect->T * B > collect->capacity)
+        return err.fail("T * B must not exceed capacity: the rows of one launch would overwrite each other");
+    for (int t = 0; t < collect->T; ++t)
+        if (!eps_ok(collect->eps[t])) return err.fail("every eps[t], t < T, must lie in [0, 1]");
+    if (B == 0) return 0;
+    if (abi::on_device(err, device)) return -1;
+    co.p = *collect;
+    if (fresh)
+        hipLaunchKernelGGL((env_step_kernel<true, true>), dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state,
+                           (const int32_t*)nullptr, out, (int)B, *fresh, co);
+    else
+        hipLaunchKernelGGL((env_step_kernel<false, true>), dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state,
+                           (const int32_t*)nullptr, out, (int)B, EnvFresh{}, co);
+    return abi::launched(err, "env_step_kernel launch");
+}
+thread_local abi::ErrorSlot g_collect_fresh_err;   // mpcgpu_collect_fresh_last_error
+
 }  // namespace envgpu
 
 extern "C" {
@@ -668,33 +708,37 @@ int32_t mpcgpu_collect_rays_dev(int32_t device, const mpcgpu_env_params* params,
                                 double* ep_return, int32_t* actions, uint8_t* done, uint8_t* success, double* episode_return,
                                 void* stream) {
     using namespace envgpu;
-    EnvK k;
-    if (const char* bad = params_error(params, k)) return collect_fail(bad);
-    if (!records || !state || !obs_internal || !obs_external || !reward || !terminated || !truncated || !terminal_obs_internal ||
-        !terminal_obs_external)
-        return collect_fail("null pointer (an environment tensor)");
-    if (!theta || !collect || !buf_obs || !buf_next_obs || !buf_actions || !buf_rewards || !buf_dones || !ep_return)
-        return collect_fail("null pointer (theta / collect / ring / ep_return)");
-    if (B < 0) return collect_fail("negative batch");
-    if (max_episode_steps <= 0) return collect_fail("max_episode_steps must be positive");
-    if (collect->T < 1 || collect->T > MPCGPU_COLLECT_MAX_STEPS) return collect_fail("1 <= T <= 64 (MPCGPU_COLLECT_MAX_STEPS)");
-    if (collect->capacity < 1 || collect->pos0 < 0 || collect->pos0 >= collect->capacity)
-        return collect_fail("capacity >= 1 and 0 <= pos0 < capacity");
-    if ((int64_t)collect->T * B > collect->capacity)
-        return collect_fail("T * B must not exceed capacity: the rows of one launch would overwrite each other");
-    for (int t = 0; t < collect->T; ++t)
-        if (!eps_ok(collect->eps[t])) return collect_fail("every eps[t], t < T, must lie in [0, 1]");
-    if (B == 0) return 0;
-    if (abi::on_device(g_collect_err, device)) return -1;
     const EnvOut out{obs_internal, obs_external, reward, terminated, truncated, terminal_obs_internal, terminal_obs_external,
                      max_episode_steps, nullptr};
     const CollectK co{theta, buf_obs, buf_next_obs, buf_actions, buf_rewards, buf_dones, ep_return, actions, done, success,
-                      episode_return, *collect};
-    hipLaunchKernelGGL((env_step_kernel<false, true>), dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state,
-                       (const int32_t*)nullptr, out, (int)B, EnvFresh{}, co);
-    return abi::launched(g_collect_err, "env_step_kernel launch");
+                      episode_return, {}};
+    return launch_collect(g_collect_err, device, params, B, records, state, out, co, collect, stream, nullptr);
 }
 
 const char* mpcgpu_collect_last_error(void) { return envgpu::g_collect_err.text.c_str(); }
+
+}  // extern "C"
+
+// include/mpcgpu_collect_fresh.h
+extern "C" {
+
+int32_t mpcgpu_collect_rays_fresh_dev(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records2,
+                                      int32_t* which, int32_t* spare_ready, int32_t* loaded, int32_t* stale, double* state,
+                                      float* obs_internal, float* obs_external, double* reward, uint8_t* terminated,
+                                      uint8_t* truncated, float* terminal_obs_internal, float* terminal_obs_external,
+                                      int32_t max_episode_steps, const float* theta, const mpcgpu_collect_params* collect,
+                                      float* buf_obs, float* buf_next_obs, int64_t* buf_actions, float* buf_rewards,
+                                      float* buf_dones, double* ep_return, int32_t* actions, uint8_t* done, uint8_t* success,
+                                      double* episode_return, void* stream) {
+    using namespace envgpu;
+    const EnvOut out{obs_internal, obs_external, reward, terminated, truncated, terminal_obs_internal, terminal_obs_external,
+                     max_episode_steps, nullptr};
+    const CollectK co{theta, buf_obs, buf_next_obs, buf_actions, buf_rewards, buf_dones, ep_return, actions, done, success,
+                      episode_return, {}};
+    const EnvFresh fresh{which, spare_ready, loaded, stale};
+    return launch_collect(g_collect_fresh_err, device, params, B, records2, state, out, co, collect, stream, &fresh);
+}
+
+const char* mpcgpu_collect_fresh_last_error(void) { return envgpu::g_collect_fresh_err.text.c_str(); }
 
 }  // extern "C"

@@ -414,7 +414,7 @@ class DqnLearner:
                  exploration_initial_eps: float = 1.0, exploration_final_eps: float = 0.05, seed: int = 0,
                  use_graph: bool = False, track_episodes: bool = True, per: bool = False,
                  per_kwargs: Optional[Dict] = None, fused: bool = False, per_in_kernel: bool = False,
-                 collect_in_kernel: bool = False, collect_launch_steps: Optional[int] = None):
+                 collect_in_kernel: bool = False, collect_launch_steps: Optional[int] = None, collect_turnover: bool = False):
         """``per=True``: prioritized experience replay (the reference's ``'per': True``): the buffer keeps a sum tree of
         priorities (``per_kwargs``: alpha, beta, epsilon, update_max_freq, initial_priority), minibatches are drawn by
         priority, the loss is weighted by the importance weights and the drawn rows are re-prioritized with their TD errors
@@ -433,9 +433,18 @@ class DqnLearner:
         ``collect_in_kernel=True`` (ray environment on one record table, any ray trainer): the ``train_freq`` steps a round of
         ``learn`` collects -- act, auto-reset step, buffer rows, episode returns -- are ONE launch of the step kernel
         (:func:`collect.collect_rays`), or launches of ``collect_launch_steps`` steps each (at most 64; the
-        default is the whole round).  Exploration then draws from the counter stream ``(collect_seed, collect_serial)``, both
+        default is the whole round, under ``collect_turnover`` ``collect_fresh.DEFAULT_LAUNCH_STEPS``).  Exploration then draws from the counter stream ``(collect_seed, collect_serial)``, both
         part of ``state_dict``, instead of the torch generator, so the actions are not those of the host-driven loop; the
-        target network is synchronised once behind a round whose steps reach the interval."""
+        target network is synchronised once behind a round whose steps reach the interval.
+
+        ``collect_turnover=True`` (needs ``collect_in_kernel=True`` and a ray environment after ``enable_spares()`` /
+        ``enable_fresh_maps()``): the launches are those of :func:`collect_fresh.collect_rays_fresh` on the two-record table
+         -- a new map per episode without leaving the launch.  A refill of the spares stands behind a launch, never
+        inside it: the run equals the one in launches of one step only where every refill point falls on the end of a launch
+        (``refill_every`` a multiple of ``collect_launch_steps``, rounds that are whole launches)."""
+        if collect_turnover and not collect_in_kernel:
+            raise ValueError("collect_turnover=True needs collect_in_kernel=True: it is collection inside the launch on the "
+                             "two-record table")
         if per_in_kernel and not (fused and per):
             raise ValueError("per_in_kernel=True needs fused=True and per=True: it is the prioritized form of the fused K-step launch")
         self.env, self.device = env, env.device
@@ -486,14 +495,16 @@ class DqnLearner:
         # state of the collection loop between two learn() calls (a run can be checkpointed and resumed in the middle)
         self._obs, self._ep_return, self.n_updates = None, None, 0
         self._last_loss = torch.zeros((), device=self.device)
-        self.collect_in_kernel = bool(collect_in_kernel)
+        self.collect_in_kernel, self.collect_turnover = bool(collect_in_kernel), bool(collect_turnover)
         if self.collect_in_kernel:
-            from . import collect, dqn_fused
-            collect.check_env(env)
+            from . import collect, collect_fresh, dqn_fused
+            (collect_fresh if self.collect_turnover else collect).check_env(env)
+            self._collect_launch = collect_fresh.collect_rays_fresh if self.collect_turnover else collect.collect_rays
             dqn_fused.check_shape(self.trainer.q_net)
             if collect_launch_steps is not None and int(collect_launch_steps) < 1:
                 raise ValueError("collect_launch_steps must be at least 1")
-            self.collect_launch_steps = collect.MAX_STEPS if collect_launch_steps is None else min(int(collect_launch_steps), collect.MAX_STEPS)
+            default = collect_fresh.DEFAULT_LAUNCH_STEPS if self.collect_turnover else collect.MAX_STEPS
+            self.collect_launch_steps = default if collect_launch_steps is None else min(int(collect_launch_steps), collect.MAX_STEPS)
             # not the trainer's fused_seed (seed + rank): minibatch rows and exploration must not share a stream
             self.collect_seed, self.collect_serial = ((seed + rank) ^ 0x436F6C6C65637421) % 2 ** 64, 0
             self._collect_out = None
@@ -629,7 +640,7 @@ class DqnLearner:
             T = min(n - made, self.collect_launch_steps)
             eps = [exploration_rate(self.num_timesteps + t * B, total_timesteps, *self.eps) for t in range(T)]
             out = {name: x[:T] for name, x in self._collect_out.items()}
-            collect.collect_rays(self.env, theta, self.buffer, eps, self.collect_seed, self.collect_serial, ep_return, out)
+            self._collect_launch(self.env, theta, self.buffer, eps, self.collect_seed, self.collect_serial, ep_return, out)
             done, ended = out["done"].bool(), out["episode_return"]
             self._account_episodes(done, out["success"].bool(), ended)
             if not self.track_episodes:       # per step, as the host-driven round sums: the same bits whatever the launch size

@@ -482,11 +482,19 @@ class BatchedRaysEnv:
             # itself, read max_steps = 0 as "no auto-reset"
             raise MpcGpuError("max_episode_steps must be positive")
         self._launch(actions, int(self.max_episode_steps))
-        if getattr(self, "refill_every", 0):     # behind the launch or launches of the step: see include/mpcgpu_map.h
-            self._calls += 1
-            if self._calls % self.refill_every == 0:
-                self.refill()
+        self._count_autoreset_steps(1)
         return self._autoreset_result()
+
+    def _count_autoreset_steps(self, n: int) -> None:
+        """The refill cadence of :meth:`enable_fresh_maps`, behind the launch or launches that made ``n`` auto-reset steps (see
+        include/mpcgpu_map.h): ONE refill if the count of steps passed a multiple of ``refill_every``.  ``n = 1`` is every
+        ``refill_every``-th step; a launch of ``n`` steps (``collect_fresh.collect_rays_fresh``) is followed by at most one
+        refill, since a second one would find the same rows missing."""
+        if getattr(self, "refill_every", 0):
+            before = self._calls
+            self._calls += int(n)
+            if before // self.refill_every != self._calls // self.refill_every:
+                self.refill()
 
     def _autoreset_result(self):
         torch = self._torch
