@@ -5,6 +5,7 @@
                               [--save DIR] [--resume DIR/checkpoint.pt] [--checkpoint-every STEPS]
                               [--images] [--fresh-maps] [--per] [--buffer-size N] [--graph | --fused [--per-in-kernel]]
                               [--collect-in-kernel | --fresh-maps --collect-turnover]
+                              [--eval-freq STEPS [--eval-envs M] [--eval-episodes E]]
 
 `--images` trains dqn.ImageQNetwork on the image environment (rl_env.BatchedImgsEnv); with `--fresh-maps` every episode of it
 starts on a new random map too (map_turnover=True, capacity map_stream.DYNAMIC_CAPACITY, stream seed + rank).
@@ -21,6 +22,12 @@ forty launches per step; exploration then draws from a counter stream of its own
 `--fresh-maps --collect-turnover` (ray environment) does the same on the two-record table of the map stream
 (collect_fresh.collect_rays_fresh): a row whose episode ends inside a launch moves to its new map there; the
 refill of the spares follows a launch, never splits it.
+
+`--eval-freq STEPS` (ray environment) is the reference's EvalCallback (src/test_block_rl.py:65-99) on the device: every STEPS
+environment steps the greedy policy plays `--eval-episodes` episodes on each of `--eval-envs` maps of a separate environment
+inside the step kernel (evaluate.EvalCallback).  best_model.pt is then chosen by the mean evaluation return,
+`--save DIR` also receives evaluations.npz (timesteps, results, ep_lengths, successes) and, for `--resume`, the callback's state
+in eval_callback.pt beside the checkpoint.  The training run itself is the run without the flag, bit for bit.
 
 `--save DIR` writes what the reference's run leaves behind (src/test_block_rl.py:73-76,89-96: EvalCallback's best_model and
 model.save's final_model) -- best_model.pt whenever the mean return of a progress window improves, final_model.pt at the end --
@@ -120,7 +127,15 @@ def parse_args(argv=None):
                     help="train dqn.ImageQNetwork on the image environment (BatchedImgsEnv); combines with --fresh-maps and --per")
     ap.add_argument("--buffer-size", type=int, default=None,
                     help="replay transitions (default 2000000; 200000 with --images, whose transitions hold two uint8 images)")
+    ap.add_argument("--eval-freq", type=int, default=0,
+                    help="environment steps between greedy evaluations on a separate environment (evaluate.EvalCallback); 0: off")
+    ap.add_argument("--eval-envs", type=int, default=64, help="maps of the evaluation environment")
+    ap.add_argument("--eval-episodes", type=int, default=1, help="evaluation episodes per map")
     args = ap.parse_args(argv)
+    if args.eval_freq < 0 or (args.eval_freq and (args.eval_envs < 1 or args.eval_episodes < 1)):
+        ap.error("--eval-freq must not be negative; --eval-envs and --eval-episodes must be at least 1")
+    if args.eval_freq and args.images:
+        ap.error("--eval-freq evaluates inside the step kernel of the ray environment: not with --images")
     if args.per_in_kernel and not (args.fused and args.per):
         ap.error("--per-in-kernel is the prioritized form of the fused K-step launch: it needs --fused and --per")
     if args.per_in_kernel and args.gpus > 1:
@@ -169,8 +184,20 @@ def main():
                                    collect_in_kernel=args.collect_in_kernel or args.collect_turnover,
                                    collect_turnover=args.collect_turnover)
     ck_name = "checkpoint.pt" if rank == 0 else f"checkpoint.rank{rank}.pt"
+    eval_cb, eval_name = None, "eval_callback.pt" if rank == 0 else f"eval_callback.rank{rank}.pt"
+    if args.eval_freq:
+        # EvalCallback of the reference's run: greedy episodes on maps of their own (a generator of its own, so the training maps
+        # are the ones of a run without it), every rank on its own environment; rank 0 writes best_model.pt and evaluations.npz
+        evaluate = importlib.import_module("trajtrack_mpcndqn_rlboost_amd.evaluate")
+        eval_rng = np.random.default_rng(10_000 + rank)
+        eval_env = rl_env.BatchedRaysEnv([scene(eval_rng) for _ in range(args.eval_envs)], device=local, max_episode_steps=400)
+        files = args.save if rank == 0 else None
+        eval_cb = evaluate.EvalCallback(eval_env, args.eval_freq, n_eval_episodes=args.eval_episodes, best_model_save_path=files,
+                                        log_path=files, seed=0x45564131 + rank)
     if args.resume:
         learner.load(args.resume if rank == 0 else os.path.join(os.path.dirname(args.resume), ck_name))
+        if eval_cb is not None and os.path.exists(os.path.join(os.path.dirname(args.resume), eval_name)):
+            eval_cb.load_state_dict(torch.load(os.path.join(os.path.dirname(args.resume), eval_name), weights_only=True))
         if rank == 0:
             print(f"  resumed at {learner.num_timesteps} environment steps, {learner.trainer.num_updates} updates", flush=True)
     if args.save:
@@ -186,19 +213,35 @@ def main():
             marks.append((lr.num_timesteps, (r - pr) / dn, (ok - pok) / dn, time.perf_counter() - t0, n, r, ok))
             if rank == 0:
                 print(f"  {marks[-1][0]:>9d} steps  mean return {marks[-1][1]:8.2f}  success {marks[-1][2]:.2f}  {marks[-1][3]:6.1f} s", flush=True)
-                if args.save and marks[-1][1] > best[0]:       # EvalCallback(best_model_save_path=...)
+                if args.save and eval_cb is None and marks[-1][1] > best[0]:       # EvalCallback(best_model_save_path=...)
                     best[0] = marks[-1][1]
                     learner.save_model(os.path.join(args.save, "best_model.pt"))
+
+    def both(lr):
+        progress(lr)
+        before = eval_cb.n_evaluations
+        eval_cb(lr)
+        if rank == 0 and eval_cb.n_evaluations != before:
+            print(f"  {lr.num_timesteps:>9d} steps  evaluation {eval_cb.n_evaluations}: mean return {eval_cb.last_mean_reward:8.2f} "
+                  f"(best {eval_cb.best_mean_reward:.2f}), success {float(np.mean(eval_cb.successes[-1])):.2f}, "
+                  f"mean length {float(np.mean(eval_cb.ep_lengths[-1])):.1f}", flush=True)
+
+    callback = progress if eval_cb is None else both
+
+    def checkpoint():
+        learner.save(os.path.join(args.save, ck_name))
+        if eval_cb is not None:
+            torch.save(eval_cb.state_dict(), os.path.join(args.save, eval_name))
 
     if args.save and args.checkpoint_every > 0:
         stats = None
         while learner.num_timesteps < args.timesteps:
-            stats = learner.learn(args.timesteps, callback=progress, stop_at=learner.num_timesteps + args.checkpoint_every)
-            learner.save(os.path.join(args.save, ck_name))
+            stats = learner.learn(args.timesteps, callback=callback, stop_at=learner.num_timesteps + args.checkpoint_every)
+            checkpoint()
     else:
-        stats = learner.learn(args.timesteps, callback=progress)
+        stats = learner.learn(args.timesteps, callback=callback)
     if args.save:
-        learner.save(os.path.join(args.save, ck_name))
+        checkpoint()
         if rank == 0:
             learner.save_model(os.path.join(args.save, "final_model.pt"))
     torch.cuda.synchronize()
@@ -223,6 +266,7 @@ def main():
                                      "per": bool(args.per), "images": bool(args.images), "fresh_maps": bool(args.fresh_maps),
                                      "collect_in_kernel": bool(args.collect_in_kernel),
                                      "collect_turnover": bool(args.collect_turnover),
+                                     "eval_freq": args.eval_freq, "evaluations": eval_cb.n_evaluations if eval_cb else 0,
                                      "buffer_size": buffer_size},
                           "success_rate": stats["success_rate"], "mean_return": stats["mean_return"]}))
     if world > 1:

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "../../include/mpcgpu_collect_fresh.h"
+#include "../../include/mpcgpu_eval.h"
 #include "dqn_act.hpp"
 #include "envgpu_internal.hpp"
 
@@ -110,8 +111,18 @@ struct CollectK {
     mpcgpu_collect_params p;
 };
 struct NoCollect {};
+// EVAL (include/mpcgpu_eval.h): the policy, the progress vectors and the [B][E] outputs
+struct EvalK {
+    const float* theta;
+    int32_t* episodes_done; int64_t* steps_done; double* ep_return; int32_t* ep_length;
+    double* returns; int32_t* lengths; uint8_t* outcome;
+    mpcgpu_eval_params p;
+};
 __device__ __forceinline__ int collect_steps(const CollectK& co) { return co.p.T; }
+__device__ __forceinline__ int collect_steps(const EvalK& co) { return co.p.max_steps; }
 __device__ __forceinline__ int collect_steps(const NoCollect&) { return 1; }
+__device__ __forceinline__ int eval_episodes(const EvalK& co) { return co.p.episodes; }
+template <class K> __device__ __forceinline__ int eval_episodes(const K&) { return 0; }
 __device__ __forceinline__ dqnact::ActLds& collect_lds() {   // LDS of the instantiations that call it only
     __shared__ dqnact::ActLds lds;
     return lds;
@@ -123,15 +134,20 @@ __device__ __forceinline__ dqnact::ActLds& collect_lds() {   // LDS of the insta
 // the observation the previous step left in global memory, after it the transition goes into the ring.  Every trip reads the
 // state and writes it back exactly as a launch of its own does, so T trips are T launches; everything COLLECT adds sits under
 // `if constexpr`, and without it the loop is `do { } while (false)`.
+// EVAL (include/mpcgpu_eval.h): the same trips with one eps, the serial taken from steps_done[b], and the episode bookkeeping in
+// place of the ring; a parked row returns before it reads anything else, and the loop ends with the row's E-th episode or after
+// co.p.max_steps trips, whichever comes first -- both bounds are arguments, no trip waits for anything.  ACTS = COLLECT or EVAL.
 // FRESH and COLLECT (include/mpcgpu_collect_fresh.h): rec, n_path, n_obst, n_edge, gx and gy are carried from trip to trip and change
 // in the turnover block alone, which reads which[b] and spare_ready[b] from global memory in every trip -- lane 0 may have rewritten
 // them in an earlier trip of this launch; the workgroup fence and the barrier in front of the ring stores stand between that store and
 // these reads.  One spare per row: the first ending of a row in a launch takes it, every later one resets on the map the row is on
 // and counts stale[b], as T launches without a refill between them do.
-template <bool FRESH, bool COLLECT = false>
+template <bool FRESH, bool COLLECT = false, bool EVAL = false>
 __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double* __restrict__ rec_all, double* state_all,
                                                         const int32_t* __restrict__ action, EnvOut out, int B, EnvFresh fr,
-                                                        std::conditional_t<COLLECT, CollectK, NoCollect> co) {
+                                                        std::conditional_t<EVAL, EvalK, std::conditional_t<COLLECT, CollectK, NoCollect>> co) {
+    static_assert(!(EVAL && (COLLECT || FRESH)), "the evaluation mode is built for one record table and has no ring");
+    constexpr bool ACTS = COLLECT || EVAL;
     float* const obs_int = out.obs_int;
     float* const obs_ext = out.obs_ext;
     double* const reward = out.reward;
@@ -140,6 +156,13 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
     __shared__ __attribute__((aligned(16))) double dirs[16][2];
     const int b = blockIdx.x;
     if (b >= B) return;
+    int ep_done = 0, ep_len = 0;
+    if constexpr (EVAL) {
+        ep_done = co.episodes_done[b];
+        // parked: the only word of the row this wavefront touches (a negative count, which no launch leaves, parks the row too:
+        // it would index in front of the row's slots)
+        if ((unsigned)ep_done >= (unsigned)co.p.episodes) return;
+    }
     const int lane = threadIdx.x;
     const double* rec = rec_all + (size_t)b * k.rec;
     if constexpr (FRESH) rec = rec_all + ((size_t)fr.which[b] * B + b) * k.rec;
@@ -149,12 +172,17 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
     double gx = rec[3], gy = rec[4];
     int t = 0, chosen = 0;
     double ep_ret = 0.0;
-    if constexpr (COLLECT) {
+    uint64_t steps_made = 0;
+    if constexpr (ACTS) {
         dqnact::stage_theta(collect_lds(), co.theta, lane, WAVE);
         ep_ret = co.ep_return[b];
     }
+    if constexpr (EVAL) {
+        ep_len = co.ep_length[b];
+        steps_made = (uint64_t)co.steps_done[b];
+    }
     do {
-    if constexpr (COLLECT) {
+    if constexpr (ACTS) {
         // ---- the action (include/mpcgpu_collect.h): the flat observation, external then internal, into LDS.  From the second trip
         //      on it is what this workgroup wrote: the fence and the barrier in front of the ring stores below cover these reads too
         dqnact::ActLds& L = collect_lds();
@@ -162,14 +190,15 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
         if (lane < MPCGPU_ENV_EXTERNAL_OBS) L.x[lane] = obs_ext[(size_t)b * MPCGPU_ENV_EXTERNAL_OBS + lane];
         else if (lane < dqnact::OBS) L.x[lane] = obs_int[(size_t)b * MPCGPU_ENV_INTERNAL_OBS + lane - MPCGPU_ENV_EXTERNAL_OBS];
         __syncthreads();
-        chosen = dqnact::act(L, lane, co.p.eps[t], co.p.seed, co.p.serial0 + (uint64_t)t, (uint64_t)b);
+        if constexpr (EVAL) chosen = dqnact::act(L, lane, co.p.eps, co.p.seed, co.p.serial0 + steps_made, (uint64_t)b);
+        else chosen = dqnact::act(L, lane, co.p.eps[t], co.p.seed, co.p.serial0 + (uint64_t)t, (uint64_t)b);
     }
     double x = st[0], y = st[1], th = st[2], v = st[3], w = st[4], clock = st[5];
     double last_prog = st[6], steps = st[25];
     int flags = (int)st[7];
     bool act = action != nullptr;
     double ts = P.time_step;
-    if constexpr (COLLECT) {
+    if constexpr (ACTS) {
         act = true;
         // The time step must not be a loop invariant: the compiler would hoist products such as ts * P.angacc_max out of the loop over
         // t, and a product formed up there is no longer fused into the addition it feeds (-ffp-contract=fast fuses within a block),
@@ -180,7 +209,7 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
     // ---- obstacles' clock and the robot (environment.py:199-203, agent.py:97-139); every lane keeps the same copy
     if (act) {
         int a;
-        if constexpr (COLLECT) a = chosen;
+        if constexpr (ACTS) a = chosen;
         else a = action[b];
         clock += ts;
         const int row = a / 3, col = a % 3;
@@ -529,9 +558,31 @@ __global__ __launch_bounds__(WAVE, 4) void env_step_kernel(EnvK k, const double*
         }
         if (ended) ep_ret = 0.0;
     }
-    } while (COLLECT && ++t < collect_steps(co));
-    if constexpr (COLLECT) {
+    if constexpr (EVAL) {
+        // ---- the episode bookkeeping (include/mpcgpu_eval.h), read back from what the step wrote behind the same workgroup-scope
+        //      fence and barrier as the ring stores above: lane 0 wrote these words, every lane reads them and keeps the same copy
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __syncthreads();
+        const bool trunc = out.truncated[b] != 0, ended = terminated[b] != 0 || trunc;
+        ep_ret = ep_ret + reward[b];
+        ep_len += 1;
+        steps_made += 1;
+        if (ended) {
+            if (lane == 0) {
+                const size_t slot = (size_t)b * co.p.episodes + ep_done;
+                co.returns[slot] = ep_ret;
+                co.lengths[slot] = ep_len;
+                co.outcome[slot] = (uint8_t)(((int)st[26] & 7) | (trunc ? 8 : 0));
+            }
+            ep_ret = 0.0; ep_len = 0; ep_done += 1;
+        }
+    }
+    } while (ACTS && ++t < collect_steps(co) && !(EVAL && ep_done >= eval_episodes(co)));
+    if constexpr (ACTS) {
         if (lane == 0) co.ep_return[b] = ep_ret;
+    }
+    if constexpr (EVAL) {
+        if (lane == 0) { co.episodes_done[b] = ep_done; co.steps_done[b] = (int64_t)steps_made; co.ep_length[b] = ep_len; }
     }
 }
 
@@ -639,6 +690,7 @@ int launch_collect(abi::ErrorSlot& err, int32_t device, const mpcgpu_env_params*
     return abi::launched(err, "env_step_kernel launch");
 }
 thread_local abi::ErrorSlot g_collect_fresh_err;   // mpcgpu_collect_fresh_last_error
+thread_local abi::ErrorSlot g_eval_err;            // mpcgpu_eval_last_error
 
 }  // namespace envgpu
 
@@ -740,5 +792,46 @@ int32_t mpcgpu_collect_rays_fresh_dev(int32_t device, const mpcgpu_env_params* p
 }
 
 const char* mpcgpu_collect_fresh_last_error(void) { return envgpu::g_collect_fresh_err.text.c_str(); }
+
+}  // extern "C"
+
+// include/mpcgpu_eval.h
+extern "C" {
+
+int32_t mpcgpu_eval_rays_dev(int32_t device, const mpcgpu_env_params* params, int32_t B, const double* records, double* state,
+                             float* obs_internal, float* obs_external, double* reward, uint8_t* terminated, uint8_t* truncated,
+                             float* terminal_obs_internal, float* terminal_obs_external, int32_t max_episode_steps,
+                             const float* theta, const mpcgpu_eval_params* eval, int32_t* episodes_done, int64_t* steps_done,
+                             double* ep_return, int32_t* ep_length, double* returns, int32_t* lengths, uint8_t* outcome,
+                             void* stream) {
+    using namespace envgpu;
+    abi::ErrorSlot& err = g_eval_err;
+    const EnvOut out{obs_internal, obs_external, reward, terminated, truncated, terminal_obs_internal, terminal_obs_external,
+                     max_episode_steps, nullptr};
+    EnvK k;
+    if (const char* bad = params_error(params, k)) return err.fail(bad);
+    if (!records || !state || !obs_internal || !obs_external || !reward || !terminated || !truncated || !terminal_obs_internal ||
+        !terminal_obs_external)
+        return err.fail("null pointer (an environment tensor)");
+    if (!theta || !eval) return err.fail("null pointer (theta / eval)");
+    if (!episodes_done || !steps_done || !ep_return || !ep_length)
+        return err.fail("null pointer (episodes_done / steps_done / ep_return / ep_length)");
+    if (!returns || !lengths || !outcome) return err.fail("null pointer (returns / lengths / outcome)");
+    if (B < 0) return err.fail("negative batch");
+    if (max_episode_steps <= 0) return err.fail("max_episode_steps must be positive");
+    if (eval->episodes < 1 || eval->episodes > MPCGPU_EVAL_MAX_EPISODES)
+        return err.fail("1 <= episodes <= 256 (MPCGPU_EVAL_MAX_EPISODES)");
+    if (eval->max_steps < 1 || eval->max_steps > MPCGPU_EVAL_MAX_LAUNCH_STEPS)
+        return err.fail("1 <= max_steps <= 4096 (MPCGPU_EVAL_MAX_LAUNCH_STEPS)");
+    if (!eps_ok(eval->eps)) return err.fail("eps must lie in [0, 1]");
+    if (B == 0) return 0;
+    if (abi::on_device(err, device)) return -1;
+    const EvalK co{theta, episodes_done, steps_done, ep_return, ep_length, returns, lengths, outcome, *eval};
+    hipLaunchKernelGGL((env_step_kernel<false, false, true>), dim3(B), dim3(WAVE), 0, (hipStream_t)stream, k, records, state,
+                       (const int32_t*)nullptr, out, (int)B, EnvFresh{}, co);
+    return abi::launched(err, "env_step_kernel launch");
+}
+
+const char* mpcgpu_eval_last_error(void) { return envgpu::g_eval_err.text.c_str(); }
 
 }  // extern "C"
