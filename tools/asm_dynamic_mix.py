@@ -10,6 +10,9 @@ evaluation), assigns every block the execution count of the innermost loop nest 
   spill_sgpr   v_writelane_b32 into / v_readlane_b32 out of the VGPRs the register allocator reserved for SGPR spills
   spill_vgpr   scratch_load / scratch_store (VGPR spills: the kernel has no other private memory)
   copies       v_mov_b64 / v_mov_b32 between registers (loop-carried value shuffles, not DPP)
+  cndmask      v_cndmask_b32 (gfx950 has no 64-bit select: a select of a double is two of them)
+  cnd_inplace  the v_cndmask_b32 whose destination is one of its two sources: `if (c) x = y;` or `x = c ? x : 0.0`, which one
+               64-bit move under an EXEC mask does as well (MPC_EXEC_SELECT, profiles/exec_select_ab.txt)
   valu         every VALU instruction
 
 Blocks inside an evaluation execute AT MOST once per evaluation (item loops: their trip counts are passed in), conditional blocks
@@ -85,7 +88,7 @@ def main():
     for e, nm, c in zip(ent, names, counts):
         site_count[inner(e)] = (nm, c, depth(e))
     step_hdr = None
-    cls = ("valu", "spill_sgpr", "spill_vgpr", "copies", "dpp", "f64", "salu", "lds", "vmem_other", "readlane_other")
+    cls = ("valu", "spill_sgpr", "spill_vgpr", "copies", "dpp", "f64", "salu", "lds", "vmem_other", "readlane_other", "cndmask", "cnd_inplace")
     tot = {nm: dict.fromkeys(cls, 0.0) for nm in names + ["step_body", "outside"]}
     static = {nm: dict.fromkeys(cls, 0) for nm in names + ["step_body", "outside"]}
     # region of a block: the evaluation site whose header appears among its enclosing loops (deepest first); else step loop if any depth >= 2; else outside
@@ -119,6 +122,11 @@ def main():
                 k.append("spill_vgpr")
             elif op.startswith("v_mov_b64") or (op.startswith("v_mov_b32") and "dpp" not in rest and "dpp" not in op) or op.startswith("v_accvgpr"):
                 k.append("copies")
+            if op.startswith("v_cndmask_b32"):
+                k.append("cndmask")
+                regs = [r.strip() for r in rest.split(",")]
+                if len(regs) >= 3 and regs[0] in regs[1:3]:
+                    k.append("cnd_inplace")
             if "dpp" in op or "dpp" in rest or "permlane" in op:
                 k.append("dpp")
             if "_f64" in op:
@@ -135,15 +143,15 @@ def main():
     print(f"# {args.asm}: {len(blocks)} blocks; SGPR-spill registers {sorted(spill_regs)}; evaluation call sites at lines {[e['line'] for e in ent]}")
     print(f"# per-solve execution counts: state machine {args.machine:.0f}, Lipschitz test {args.lip:.0f}, line search {args.ls:.0f} evaluations; {args.steps:.0f} PANOC steps; "
           f"inner item loops x{args.item_trips:g}")
-    print(f"{'region':10s} {'static VALU':>11s} {'dyn VALU/solve':>15s} {'SGPR spill':>12s} {'VGPR spill':>12s} {'copies':>10s} {'dpp':>10s} {'f64':>10s} {'rdlane(other)':>13s}")
+    print(f"{'region':10s} {'static VALU':>11s} {'dyn VALU/solve':>15s} {'SGPR spill':>12s} {'VGPR spill':>12s} {'copies':>10s} {'dpp':>10s} {'f64':>10s} {'rdlane(other)':>13s} {'cndmask':>8s} {'in place':>8s}")
     G = dict.fromkeys(cls, 0.0)
     for nm in names + ["step_body", "outside"]:
         t = tot[nm]
         for c in cls:
             G[c] += t[c]
-        print(f"{nm:10s} {static[nm]['valu']:11d} {t['valu']:15.3e} {t['spill_sgpr']:12.3e} {t['spill_vgpr']:12.3e} {t['copies']:10.3e} {t['dpp']:10.3e} {t['f64']:10.3e} {t['readlane_other']:13.3e}")
+        print(f"{nm:10s} {static[nm]['valu']:11d} {t['valu']:15.3e} {t['spill_sgpr']:12.3e} {t['spill_vgpr']:12.3e} {t['copies']:10.3e} {t['dpp']:10.3e} {t['f64']:10.3e} {t['readlane_other']:13.3e} {static[nm]['cndmask']:8d} {static[nm]['cnd_inplace']:8d}")
     v = G["valu"]
-    print(f"{'total':10s} {'':11s} {v:15.3e} {G['spill_sgpr']:12.3e} {G['spill_vgpr']:12.3e} {G['copies']:10.3e} {G['dpp']:10.3e} {G['f64']:10.3e} {G['readlane_other']:13.3e}")
+    print(f"{'total':10s} {'':11s} {v:15.3e} {G['spill_sgpr']:12.3e} {G['spill_vgpr']:12.3e} {G['copies']:10.3e} {G['dpp']:10.3e} {G['f64']:10.3e} {G['readlane_other']:13.3e} {sum(static[nm]['cndmask'] for nm in static):8d} {sum(static[nm]['cnd_inplace'] for nm in static):8d}")
     print(f"shares of the dynamic VALU stream (upper bounds where blocks are conditional): SGPR-spill lane moves {100 * G['spill_sgpr'] / v:.2f} %, register copies "
           f"{100 * G['copies'] / v:.2f} %, DPP {100 * G['dpp'] / v:.2f} %, f64 arithmetic {100 * G['f64'] / v:.2f} %; scratch (VGPR spill) instructions per solve "
           f"{G['spill_vgpr']:.3e} = {G['spill_vgpr'] / max(args.steps, 1):.2f} per PANOC step")

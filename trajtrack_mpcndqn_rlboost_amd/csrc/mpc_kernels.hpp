@@ -237,6 +237,28 @@ __host__ __device__ constexpr bool gram_square(int N, int mem) { return MPC_LEAN
 __host__ __device__ constexpr bool lean_items(int NT, int lanes, bool duo, int what) {
     return MPC_LEAN_ITEMS != 0 && (MPC_LEAN_ITEMS_SET & what) != 0 && NT == 20 && lanes == 64 && !duo;
 }
+// In-place selects of a double as ONE 64-bit move under an EXEC mask (N_hor = 20, one problem per wavefront; exec_select() below).
+// gfx950 has no 64-bit select: `if (c) x = y;` and `x = c ? x : 0.0` compile to two v_cndmask_b32 each, on the VALU port this kernel is
+// bound by; as a masked region they are one v_mov_b64 (or the arithmetic itself, written under the mask), and the EXEC
+// bookkeeping issues on the scalar port, which is idle.  The helpers (take_where, zero_unless, keep_masked) only copy bits: signed
+// zeros, NaN payloads and infinities as before, no floating-point operation added, removed or reordered.  0 = the former code,
+// instruction for instruction (`make variants`: libmpcgpu_sel0.so, the bitwise yardstick and A/B partner:
+// tests/test_gpu_exec_select.py).  Listing of the benchmark kernel: 317 -> 220 v_cndmask_b32, -1.62 % weighted VALU per solve, of
+// which -0.73 points are the accumulator zeros of group 32 (not a select: see below); on the MI355X against the parent build:
+// same bits, -1.0 % kernel time on the benchmark leg (profiles/exec_select_ab.txt).
+#ifndef MPC_EXEC_SELECT
+#define MPC_EXEC_SELECT 1
+#endif
+// Experiment mask of the site groups: 1 segment minimum, 2 combine, 4 zeros beyond the horizon in the evaluation, 8 half step and
+// Lipschitz perturbation, 16 accumulations under a per-lane condition in the item phase, 32 the start values of the item
+// accumulators formed once (zero_here) -- a literal start value is formed again in front of every guarded region and loop the
+// accumulator enters, which the masked regions of 16 make more of.  Each group lowers the count of the whole set; 1 and 2 do not alone.
+#ifndef MPC_EXEC_SELECT_SET
+#define MPC_EXEC_SELECT_SET 63
+#endif
+__host__ __device__ constexpr bool exec_select(int NT, int lanes, bool duo, int what) {
+    return MPC_EXEC_SELECT != 0 && (MPC_EXEC_SELECT_SET & what) != 0 && NT == 20 && lanes == 64 && !duo;
+}
 // doubles of the LDS region `gg` (Gram matrices, or the alpha scratch of the two-loop form): see fixed_lds
 __host__ __device__ constexpr int gg_doubles_c(int N, int mem, bool gram) {
     return gram ? yield_even_c(mem * mem + (gram_square(N, mem) ? mem * mem : mem * (mem + 1) / 2)) : yield_even_c(mem);
@@ -491,6 +513,24 @@ __device__ __forceinline__ double clamp_u(double x, double lo, double hi) {
 // evaluation's dependency chain.  One VALU instruction at the point of use is cheaper than that by two orders of magnitude.
 __device__ __forceinline__ double here_s(double x) { asm volatile("" : "+s"(x)); return x; }   // stays an SGPR pair
 __device__ __forceinline__ double zero_here() { double z = 0.0; asm volatile("" : "+v"(z)); return z; }
+// MPC_EXEC_SELECT: in-place selects as moves under an EXEC mask.  The empty asm inside the branch keeps the compiler from turning the
+// region back into a pair of v_cndmask_b32 per double; several doubles under one condition share one region.
+// keep_masked: the values assigned (or accumulated) inside a divergent branch stay there.
+__device__ __forceinline__ void keep_masked(double& a) { asm volatile("" : "+v"(a)); }
+__device__ __forceinline__ void keep_masked(double& a, double& b) { asm volatile("" : "+v"(a), "+v"(b)); }
+__device__ __forceinline__ void keep_masked(double& a, double& b, double& c) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c)); }
+__device__ __forceinline__ void keep_masked(double& a, double& b, double& c, double& d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
+// take y into x in the lanes where c holds
+__device__ __forceinline__ void take_where(bool c, double& x, double y) { if (c) { x = y; keep_masked(x); } }
+__device__ __forceinline__ void take_where(bool c, double& x0, double y0, double& x1, double y1, double& x2, double y2) {
+    if (c) { x0 = y0; x1 = y1; x2 = y2; keep_masked(x0, x1, x2); }
+}
+// zero x where c does not hold (+0.0, the bits of `c ? x : 0.0`)
+__device__ __forceinline__ void zero_unless(bool c, double& a) { if (!c) { a = 0.0; keep_masked(a); } }
+__device__ __forceinline__ void zero_unless(bool c, double& a, double& b) { if (!c) { a = 0.0; b = 0.0; keep_masked(a, b); } }
+__device__ __forceinline__ void zero_unless(bool c, double& a, double& b, double& d, double& e) {
+    if (!c) { a = 0.0; b = 0.0; d = 0.0; e = 0.0; keep_masked(a, b, d, e); }
+}
 
 // inclusive prefix PRODUCT of unit complex numbers (re, im) over lanes 0..16*ROWS-1 (lanes >= n carry 1+0i)
 // x moved by DPP, lanes without a source (or in rows that are masked off) receive 1.0.  The low word of 1.0 is zero: where every
@@ -1098,8 +1138,11 @@ struct SegDist {
         wx = s1x + t * dx - px; wy = s1y + t * dy - py;
         d2 = wx * wx + wy * wy;
     }
+    template <bool ES = false>   // MPC_EXEC_SELECT: the zero outside [0, 1] as a masked move
     __device__ __forceinline__ void grad(double& gx, double& gy) const {
-        const double wd = (th >= 0.0 && th <= 1.0) ? (wx * dx + wy * dy) * inv : 0.0;
+        double wd;
+        if (ES) { wd = (wx * dx + wy * dy) * inv; zero_unless(th >= 0.0 && th <= 1.0, wd); }
+        else wd = (th >= 0.0 && th <= 1.0) ? (wx * dx + wy * dy) * inv : 0.0;
         gx = 2.0 * (wd * dx - wx);
         gy = 2.0 * (wd * dy - wy);
     }
@@ -1131,6 +1174,9 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
     // MPC_LEAN_ITEMS: the candidates of the lean item phase that this instantiation takes (N_hor = 20, uniform split, one problem per wavefront)
     constexpr bool LI_ROWS = lean_items(NT, PW, P::DUO, 1), LI_ZERO = lean_items(NT, PW, P::DUO, 2), LI_ROLE = lean_items(NT, PW, P::DUO, 4),
                    LI_HDR = lean_items(NT, PW, P::DUO, 8);
+    // MPC_EXEC_SELECT: the site groups this instantiation takes
+    constexpr bool ES_SEG = exec_select(NT, PW, P::DUO, 1), ES_COMB = exec_select(NT, PW, P::DUO, 2), ES_ZERO = exec_select(NT, PW, P::DUO, 4),
+                   ES_ACC = exec_select(NT, PW, P::DUO, 16), ES_INIT = exec_select(NT, PW, P::DUO, 32);
     if (LI_ROLE) __builtin_assume(lane >= 0 && lane < WAVE);   // the lane index is opaque: 24-bit multiplies, no sign extensions
     const bool c_vl = lane < N;
     const bool c_il = UNIFORM ? lane < (PW / N) * N : true;
@@ -1144,7 +1190,8 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
     const double ts = here_s(kp.ts);
     const double fleetw = here_s(kp.fleetw);
     const double inf = __builtin_huge_val();
-    if (!c_vl) { v = 0.0; w = 0.0; }
+    if (ES_ZERO) zero_unless(c_vl, v, w);
+    else if (!c_vl) { v = 0.0; w = 0.0; }
     if (NT == 20) MPC_PRIO_CHAIN();
 
     // ---- rollout.  Heading phasors e^{i theta}: theta_{k+1} = theta_k + ts*w_k, so they are a prefix PRODUCT of
@@ -1231,6 +1278,10 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
 
     // ---- item phase A: stage terms of step ik handled by this lane
     double cost_l = 0.0, S_l = 0.0, gx = 0.0, gy = 0.0, dsx = 0.0, dsy = 0.0;
+    if (ES_INIT) {   // one zero per accumulator, formed here: a literal is formed again in front of every guarded region and loop it enters
+        cost_l = zero_here(); S_l = zero_here();
+        if (!VO) { gx = zero_here(); gy = zero_here(); dsx = zero_here(); dsy = zero_here(); }
+    }
     // (MPC_LEAN_ITEMS: the segment minimum starts inside the item lanes' region, its one definition -- no other lane reads it)
     double best, bgx, bgy;
     if (!LI_ZERO) { best = inf; bgx = 0.0; bgy = 0.0; }
@@ -1279,6 +1330,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
         const int k = c_ik;
         px = cx.pos[2 * k]; py = cx.pos[2 * k + 1];
         if (LI_ZERO) { best = inf; bgx = 0.0; bgy = 0.0; }
+        if (ES_INIT) { keep_masked(best); if (!VO) keep_masked(bgx, bgy); }   // formed once, here
         // reference-path deviation: min over segments i >= k (mpc_generator.py:207,116-130,28-36).
         // Exact pruning: segments inside a circle that is farther from the robot than sqrt(best) cannot hold the minimum
         // (nor tie with it), so their distances are not evaluated; the value and the arg-min are unchanged.
@@ -1289,6 +1341,14 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
         for (int it = 0; it < SEG_WIN && i < N; ++it, i += LPS) {
             const double* sg = cx.seg + SEGW * i;
             const SegDist sd(sg, px, py);
+            if (ES_SEG) {      // the minimum and its nearest-point gradient move together, in one masked region
+                if (VO) take_where(sd.d2 < best, best, sd.d2);
+                else {
+                    double tgx, tgy;
+                    sd.template grad<true>(tgx, tgy);
+                    take_where(sd.d2 < best, best, sd.d2, bgx, tgx, bgy, tgy);
+                }
+            } else
             if (sd.d2 < best) {
                 best = sd.d2;
                 if (!VO) sd.grad(bgx, bgy);
@@ -1337,6 +1397,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
                     gx -= 2.0 * fleetw * ex;
                     gy -= 2.0 * fleetw * ey;
                 }
+                if (ES_ACC) { if (VO) keep_masked(cost_l); else keep_masked(cost_l, gx, gy); }
             }
         }
         // static polygons (mpc_generator.py:219-225,46-54): 4 half-planes each in the kernels with a compiled horizon (and in the generic
@@ -1362,6 +1423,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
                         dsx -= r0 * s[4] + r1 * s[5] + r2 * s[6] + r3 * s[7];
                         dsy -= r0 * s[8] + r1 * s[9] + r2 * s[10] + r3 * s[11];
                     }
+                    if (ES_ACC) { if (VO) keep_masked(S_l); else keep_masked(S_l, dsx, dsy); }
                 }
             }
         } else {
@@ -1495,6 +1557,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
                     gx += wI * (-2.0 * d.a * d.ca * d.isx - 2.0 * d.b * d.sa * d.isy);
                     gy += wI * (-2.0 * d.a * d.sa * d.isx + 2.0 * d.b * d.ca * d.isy);
                 }
+                if (ES_ACC) { if (VO) keep_masked(cost_l); else keep_masked(cost_l, gx, gy); }
             }
             return Ih > 0.0;
         };
@@ -1527,6 +1590,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
                     gx += wI * (-2.0 * d.a * d.ca * d.isx - 2.0 * d.b * d.sa * d.isy);
                     gy += wI * (-2.0 * d.a * d.sa * d.isx + 2.0 * d.b * d.ca * d.isy);
                 }
+                if (ES_ACC) { if (VO) keep_masked(cost_l); else keep_masked(cost_l, gx, gy); }
             }
             return Ih > 0.0;
         };
@@ -1594,7 +1658,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
         r2o = X * X + Y * Y;
         if (cx.pad_f) {
             const double hh = kp.W2 - r2o;
-            if (hh > 0.0) cost_l += fleetw * HD(H_NPF) * hh;  // its gradient is added on the vector lanes below
+            if (hh > 0.0) { cost_l += fleetw * HD(H_NPF) * hh; if (ES_ACC) keep_masked(cost_l); }  // its gradient is added on the vector lanes below
         }
         if (cx.pad_d) {
             const double ipad = KC(K_IPAD);
@@ -1736,6 +1800,7 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
             if (any_S) {
                 gx += c * sumF2 * dsx;
                 gy += c * sumF2 * dsy;
+                if (ES_ACC) keep_masked(gx, gy);
             }
         }
         if (any_hp && hp > 0.0) {  // a = X, b = -Y for the padded ellipse (cosA = 1, sinA = 0)
@@ -1760,10 +1825,12 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
     if (VO) {
         if (c_vl) {   // the minimum alone, folded by the comparisons of the general form
             double bb = inf;
-            if (best < bb) bb = best;
+            if (ES_COMB) { bb = best; take_where(!(best < inf), bb, inf); }   // `best` is dead from here on: the start value moves in where no segment was found
+            else if (best < bb) bb = best;
             for (int s = 1; s < LPS; ++s) {
                 const double b2 = cx.part[((s - 1) * N + lane) * PARTW + 2];
-                if (b2 < bb) bb = b2;
+                if (ES_COMB) take_where(b2 < bb, bb, b2);
+                else if (b2 < bb) bb = b2;
             }
             vcost = HD(H_QRPD) * bb;
         }
@@ -1771,10 +1838,19 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
         double bb = inf, wbx = 0.0, wby = 0.0;
         bool tie = false;
         Gx += gx; Gy += gy;
-        if (best < bb) { bb = best; wbx = bgx; wby = bgy; }
+        if (ES_COMB) {     // (best, bgx, bgy) are dead from here on: the start values move in where no segment was found
+            bb = best; wbx = bgx; wby = bgy;
+            take_where(!(best < inf), bb, inf, wbx, 0.0, wby, 0.0);
+        } else if (best < bb) { bb = best; wbx = bgx; wby = bgy; }
         for (int s = 1; s < LPS; ++s) {
             const double* pp = cx.part + ((s - 1) * N + lane) * PARTW;
             Gx += pp[0]; Gy += pp[1];
+            if (ES_COMB) {     // the three moves in one masked region; where the minimum did not move it is the one pp[2] was compared
+                const double p2 = pp[2];   // against, so the tie test reads it afterwards and no copy of the former minimum is kept
+                const bool less = p2 < bb;
+                take_where(less, bb, p2, wbx, pp[3], wby, pp[4]);
+                if (!less && p2 == bb) tie = true;
+            } else
             if (pp[2] < bb) { bb = pp[2]; wbx = pp[3]; wby = pp[4]; }
             else if (pp[2] == bb) tie = true;
         }
@@ -1841,8 +1917,12 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
     }
     // psi = f + c/2 dist^2_C(F1 + y/max(c,1)) + c/2 ||F2||^2 in ONE wave reduction of per-lane partials
     // (item lanes: stage costs; vector lanes: per-step costs + box distance; lanes < Kd: their F2 entry)
-    const double dist_l = c_vl ? ea * ea + eb * eb : 0.0;
-    const double f2_l = viol ? F2e * F2e : 0.0;
+    double dist_l;
+    if (ES_ZERO) { dist_l = ea * ea + eb * eb; zero_unless(c_vl, dist_l); }
+    else dist_l = c_vl ? ea * ea + eb * eb : 0.0;
+    double f2_l;
+    if (ES_ZERO) { f2_l = F2e * F2e; zero_unless(viol, f2_l); }
+    else f2_l = viol ? F2e * F2e : 0.0;
     const double pad2 = viol ? HD(H_NPD) * F2pad * F2pad : 0.0;
     out.psi = P::template sum<RI>(cost_l + vcost + 0.5 * c * (dist_l + f2_l)) + 0.5 * c * pad2;
     if (want_f) {  // f and ||F2||^2 on their own (outer loop, test hook): two more reductions
@@ -1852,8 +1932,15 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
 
     PROF_MARK(8);  // vector terms + psi
     if (want_grad) {
-        const double da = c_vl ? ((LI_HDR ? HD(H2_ACC) : 2.0 * HD(H_ACC)) * a + c * ea) * kp.inv_ts : 0.0;
-        const double db = c_vl ? ((LI_HDR ? HD(H2_WACC) : 2.0 * HD(H_WACC)) * bacc + c * eb) * kp.inv_ts : 0.0;
+        double da, db;
+        if (ES_ZERO) {
+            da = ((LI_HDR ? HD(H2_ACC) : 2.0 * HD(H_ACC)) * a + c * ea) * kp.inv_ts;
+            db = ((LI_HDR ? HD(H2_WACC) : 2.0 * HD(H_WACC)) * bacc + c * eb) * kp.inv_ts;
+            zero_unless(c_vl, da, db);
+        } else {
+            da = c_vl ? ((LI_HDR ? HD(H2_ACC) : 2.0 * HD(H_ACC)) * a + c * ea) * kp.inv_ts : 0.0;
+            db = c_vl ? ((LI_HDR ? HD(H2_WACC) : 2.0 * HD(H_WACC)) * bacc + c * eb) * kp.inv_ts : 0.0;
+        }
         const double da_n = shift_down1(da), db_n = shift_down1(db);
         double gv = (LI_HDR ? HD(H2_QVEL) : 2.0 * HD(H_QVEL)) * (v - cx.vref) + (LI_HDR ? HD(H2_RV) : 2.0 * HD(H_RV)) * v + da - da_n;
         double gw = (LI_HDR ? HD(H2_RW) : 2.0 * HD(H_RW)) * w + db - db_n;
@@ -1867,8 +1954,11 @@ __device__ __forceinline__ void eval_point(const KParams& kp, const Ctx& cx, dou
         const double Bx = P::template suffix<RV>(T, lane) - T;
         gv += ts * (Cx * Ax + Sy * Ay);
         gw += ts * v * (dCw * Ax + dSw * Ay) + ts * (Bx + gthN);
+        if (ES_ZERO) { zero_unless(c_vl, gv, gw); out.gv = gv; out.gw = gw; }
+        else {
         out.gv = c_vl ? gv : 0.0;
         out.gw = c_vl ? gw : 0.0;
+        }
     }
     PROF_MARK(9);  // adjoint
 }
@@ -1957,8 +2047,15 @@ __device__ __forceinline__ double dot2r(double a0, double a1, double b0, double 
     return P::template sum<ROWS>(__builtin_fma(a0, b0, a1 * b1));
 }
 // perturbation of the local Lipschitz estimate: h_i = max(delta, eps * u_i); nh = ||h||
-template <class P>
+template <class P, bool ES = false>
 __device__ __forceinline__ void panoc_lip_perturbation(const Ctx& cx, bool vl, double uv, double uw, double& h0, double& h1, double& nh) {
+    if (ES) {   // MPC_EXEC_SELECT: the same values, the zeros beyond the horizon as masked moves
+        h0 = (KC(K_EPS_LIP) * uv > KC(K_DELTA_LIP)) ? KC(K_EPS_LIP) * uv : KC(K_DELTA_LIP);
+        h1 = (KC(K_EPS_LIP) * uw > KC(K_DELTA_LIP)) ? KC(K_EPS_LIP) * uw : KC(K_DELTA_LIP);
+        zero_unless(vl, h0, h1);
+        nh = P::uni(sqrt(dot2r<P, P::RV>(h0, h1, h0, h1)));
+        return;
+    }
     h0 = vl ? ((KC(K_EPS_LIP) * uv > KC(K_DELTA_LIP)) ? KC(K_EPS_LIP) * uv : KC(K_DELTA_LIP)) : 0.0;
     h1 = vl ? ((KC(K_EPS_LIP) * uw > KC(K_DELTA_LIP)) ? KC(K_EPS_LIP) * uw : KC(K_DELTA_LIP)) : 0.0;
     nh = P::uni(sqrt(dot2r<P, P::RV>(h0, h1, h0, h1)));
@@ -1976,9 +2073,17 @@ __device__ __forceinline__ void panoc_lip_estimate(const Ctx& cx, double d0, dou
     sigma = P::uni(KC(K_SIGMA) * ig);
 }
 // u_half <- Proj_U(base - gamma * grad); returns this lane's share of ||gradient_step - u_half||^2
+template <bool ES = false>
 __device__ __forceinline__ double panoc_half_step(const KParams& kp, bool vl, double bv, double bw, double gamma, double g0, double g1,
                                                   double& hv, double& hw) {
     const double sv = bv - gamma * g0, sw = bw - gamma * g1;
+    if (ES) {   // MPC_EXEC_SELECT: the four zeros beyond the horizon in one masked region
+        hv = clamp_u(sv, kp.vmin, kp.vmax);
+        hw = clamp_u(sw, -kp.wmax, kp.wmax);
+        double e0 = sv - hv, e1 = sw - hw;
+        zero_unless(vl, hv, hw, e0, e1);
+        return __builtin_fma(e0, e0, e1 * e1);
+    }
     hv = vl ? clamp_u(sv, kp.vmin, kp.vmax) : 0.0;
     hw = vl ? clamp_u(sw, -kp.wmax, kp.wmax) : 0.0;
     const double e0 = vl ? sv - hv : 0.0, e1 = vl ? sw - hw : 0.0;
@@ -1986,10 +2091,10 @@ __device__ __forceinline__ double panoc_half_step(const KParams& kp, bool vl, do
 }
 // half step from (bv, bw) plus the two sums of the forward-backward envelope there, ||grad||^2 and
 // ||gradient_step - u_half||^2, in ONE packed reduction
-template <class P>
+template <class P, bool ES = false>
 __device__ __forceinline__ void panoc_envelope_sums(const KParams& kp, bool vl, double bv, double bw, double gamma, double g0, double g1,
                                                     double& hv, double& hw, double& gg, double& d2h) {
-    const double e2 = panoc_half_step(kp, vl, bv, bw, gamma, g0, g1, hv, hw);
+    const double e2 = panoc_half_step<ES>(kp, vl, bv, bw, gamma, g0, g1, hv, hw);
     P::sum2(__builtin_fma(g0, g0, g1 * g1), e2, gg, d2h);
 }
 __device__ __forceinline__ double panoc_fbe(double cost, double gamma, double ig, double gg, double d2h) {
@@ -2005,12 +2110,12 @@ __device__ __forceinline__ bool panoc_lip_test_fails(const Ctx& cx, double cost_
     return cost_half > rhs_lip;
 }
 // L <- 2L, gamma <- gamma / 2, new half step, fpr and the sums that belong to it
-template <class P>
+template <class P, bool ES = false>
 __device__ __forceinline__ void panoc_lip_update(const KParams& kp, bool vl, double uv, double uw, double gv, double gw, double& Lip,
                                                  double& gamma, double& ig, double& hv, double& hw, double& rv, double& rw, double& d2h,
                                                  double& nfpr, double& ip) {
     Lip = P::uni(Lip * 2.0); gamma = P::uni(gamma * 0.5); ig = P::uni(ig * 2.0);
-    const double e2 = panoc_half_step(kp, vl, uv, uw, gamma, gv, gw, hv, hw);
+    const double e2 = panoc_half_step<ES>(kp, vl, uv, uw, gamma, gv, gw, hv, hw);
     rv = uv - hv; rw = uw - hw;
     double rr;
     P::sum2(e2, __builtin_fma(rv, rv, rw * rw), d2h, rr);
@@ -2579,6 +2684,7 @@ __device__ __forceinline__ bool alm_stalled(const Ctx& cx, const KParams& kp, in
 // The rare evaluations are states of a small machine; the PANOC steps run in a loop of their own (MPC_STEP_LOOP).
 template <int NT, bool SC, bool LBG, class P, bool AXIS = false, bool LIN = false, int MINW = 3>
 __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& io, int B, double* lds) {
+    constexpr bool ES_STEP = exec_select(NT, P::W, P::DUO, 8);   // MPC_EXEC_SELECT: the zeros of the half step as masked moves
     if (P::problem() >= B) return;
     if (io.nsel && P::problem() >= *io.nsel) return;               // pick-up launch: only the listed problems
     const int b = io.perm ? io.perm[P::problem()] : P::problem();   // every output below is indexed by the PROBLEM, not by the workgroup
@@ -2720,12 +2826,12 @@ __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& i
             // cost + gradient at u; perturbation for the local Lipschitz estimate
             cost = P::uni(o.psi); gv = o.gv; gw = o.gw;
             double h0, h1;
-            panoc_lip_perturbation<P>(cx, vl, uv, uw, h0, h1, nh);
+            panoc_lip_perturbation<P, ES_STEP>(cx, vl, uv, uw, h0, h1, nh);
             ev = uv + h0; ew = uw + h1; want_grad = true; state = ST_INIT1;
             continue;
         } else if (state == ST_INIT1) {
             panoc_lip_estimate<P>(cx, o.gv - gv, o.gw - gw, nh, Lip, gamma, ig, sigma);
-            panoc_envelope_sums<P>(kp, vl, uv, uw, gamma, gv, gw, hv, hw, gg, d2h);
+            panoc_envelope_sums<P, ES_STEP>(kp, vl, uv, uw, gamma, gv, gw, hv, hw, gg, d2h);
             step_begin = true;
         }
 #if !MPC_STEP_LOOP
@@ -2733,7 +2839,7 @@ __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& i
             const double cost_half = o.psi;
             if (panoc_lip_test_fails(cx, cost_half, cost, ip, ig, nfpr) && lip_it < MAX_LIP_IT && Lip < KC(K_MAX_LIP)) {
                 lb.flush();  // invalidate the L-BFGS buffer
-                panoc_lip_update<P>(kp, vl, uv, uw, gv, gw, Lip, gamma, ig, hv, hw, rv_, rw_, d2h, nfpr, ip);
+                panoc_lip_update<P, ES_STEP>(kp, vl, uv, uw, gv, gw, Lip, gamma, ig, hv, hw, rv_, rw_, d2h, nfpr, ip);
                 ++lip_it;
                 ev = hv; ew = hw; want_grad = false;
                 continue;
@@ -2763,7 +2869,7 @@ __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& i
 #endif
         else if (state == ST_NOLS) {
             cost = P::uni(o.psi); gv = o.gv; gw = o.gw;
-            panoc_envelope_sums<P>(kp, vl, uv, uw, gamma, gv, gw, hv, hw, gg, d2h);
+            panoc_envelope_sums<P, ES_STEP>(kp, vl, uv, uw, gamma, gv, gw, hv, hw, gg, d2h);
 #ifdef MPC_TRACE
             tr_write(-1, 1.0);
 #endif
@@ -2774,7 +2880,7 @@ __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& i
         else if (state == ST_LS) {
             // (ev, ew) is the trial point u_plus
             cost = P::uni(o.psi); gv = o.gv; gw = o.gw;
-            panoc_envelope_sums<P>(kp, vl, ev, ew, gamma, gv, gw, hv, hw, gg, d2h);
+            panoc_envelope_sums<P, ES_STEP>(kp, vl, ev, ew, gamma, gv, gw, hv, hw, gg, d2h);
             const double lhs = panoc_fbe(cost, gamma, ig, gg, d2h);
             if (lhs > rhs && nls < MAX_LS_IT) {
                 tau = P::uni(tau * 0.5); ++nls;
@@ -2875,7 +2981,7 @@ __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& i
                     const double cost_half = o.psi;
                     if (panoc_lip_test_fails(cx, cost_half, cost, ip, ig, nfpr) && lip_it < MAX_LIP_IT && Lip < KC(K_MAX_LIP)) {
                         lb.flush();  // invalidate the L-BFGS buffer
-                        panoc_lip_update<P>(kp, vl, uv, uw, gv, gw, Lip, gamma, ig, hv, hw, rv_, rw_, d2h, nfpr, ip);
+                        panoc_lip_update<P, ES_STEP>(kp, vl, uv, uw, gv, gw, Lip, gamma, ig, hv, hw, rv_, rw_, d2h, nfpr, ip);
                         ++lip_it;
                         continue;
                     }
@@ -2899,7 +3005,7 @@ __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& i
                     ++n_eval; ++n_eval_grad;
                     eval_point<NT, SC, P, AXIS, LIN, MINW>(kp, cx, ev, ew, c, icm, ya, yb, true, false, o PROF_PASS);
                     cost = P::uni(o.psi); gv = o.gv; gw = o.gw;
-                    panoc_envelope_sums<P>(kp, vl, ev, ew, gamma, gv, gw, hv, hw, gg, d2h);
+                    panoc_envelope_sums<P, ES_STEP>(kp, vl, ev, ew, gamma, gv, gw, hv, hw, gg, d2h);
                     const double lhs = panoc_fbe(cost, gamma, ig, gg, d2h);
                     if (lhs > rhs && nls < MAX_LS_IT) {
                         tau = P::uni(tau * 0.5); ++nls;

@@ -72,6 +72,7 @@ template <int NT, int TW>
 __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KParams kp, BatchPtrs io, int B) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     using P = Solo<NT>;
+    constexpr bool ES_STEP = exec_select(NT, P::W, P::DUO, 8);   // MPC_EXEC_SELECT: the zeros of the half step as masked moves
     constexpr bool SC = false;  // general tables: no batch-wide shape information is needed before the launch
     const int N = NT ? NT : kp.N;  // compile-time horizon (0 = runtime horizon from KParams)
     const bool resume = io.ylist != nullptr;
@@ -337,7 +338,7 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
             if (wid == 0) {
                 flag = (panoc_lip_test_fails(cx, o.psi, cost, ip, ig, nfpr) && lip_it < MAX_LIP_IT && Lip < KC(K_MAX_LIP)) ? 1.0 : 0.0;
             } else {
-                panoc_envelope_sums<P>(kp, vl, ev, ew, gamma, o.gv, o.gw, thv, thw, tgg, td2h);
+                panoc_envelope_sums<P, ES_STEP>(kp, vl, ev, ew, gamma, o.gv, o.gw, thv, thw, tgg, td2h);
                 flag = panoc_fbe(uniform(o.psi), gamma, ig, tgg, td2h) > rhs ? 0.0 : 1.0;  // 1 = accepted
             }
             double all[TW];
@@ -349,7 +350,7 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
                 // the one-wavefront kernel never stored this pair.
                 lb.flush();
                 lb.head = head_spec;
-                panoc_lip_update<P>(kp, vl, uv, uw, gv, gw, Lip, gamma, ig, hv, hw, rv_, rw_, d2h, nfpr, ip);
+                panoc_lip_update<P, ES_STEP>(kp, vl, uv, uw, gv, gw, Lip, gamma, ig, hv, hw, rv_, rw_, d2h, nfpr, ip);
                 ++lip_it;
                 ev = hv; ew = hw; want_grad = false; state = TS_LIPSEQ;
                 return 0;
@@ -377,7 +378,7 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
     auto batch_verdict = [&]() -> int {
             // trials t0 + wid, tau = 2^-t; t = MAX_LS_IT is taken unconditionally (ls_fallback = 0) or leads to the tau = 0 point
             double thv, thw, tgg, td2h;
-            panoc_envelope_sums<P>(kp, vl, ev, ew, gamma, o.gv, o.gw, thv, thw, tgg, td2h);
+            panoc_envelope_sums<P, ES_STEP>(kp, vl, ev, ew, gamma, o.gv, o.gw, thv, thw, tgg, td2h);
             const int t = t0 + wid;
             const bool accepted = !(panoc_fbe(uniform(o.psi), gamma, ig, tgg, td2h) > rhs);
             const double flag = t > MAX_LS_IT ? 0.0 : (accepted ? 1.0 : (t == MAX_LS_IT ? 2.0 : 0.0));  // 2 = last trial, rejected
@@ -422,13 +423,13 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
             ++n_eval; ++n_eval_grad;
             cost = uniform(o.psi); gv = o.gv; gw = o.gw;
             double h0, h1;
-            panoc_lip_perturbation<P>(cx, vl, uv, uw, h0, h1, nh);
+            panoc_lip_perturbation<P, ES_STEP>(cx, vl, uv, uw, h0, h1, nh);
             ev = uv + h0; ew = uw + h1; want_grad = true; state = TS_INIT1;
             continue;
         } else if (state == TS_INIT1) {
             ++n_eval; ++n_eval_grad;
             panoc_lip_estimate<P>(cx, o.gv - gv, o.gw - gw, nh, Lip, gamma, ig, sigma);
-            panoc_envelope_sums<P>(kp, vl, uv, uw, gamma, gv, gw, hv, hw, gg, d2h);
+            panoc_envelope_sums<P, ES_STEP>(kp, vl, uv, uw, gamma, gv, gw, hv, hw, gg, d2h);
             step_begin = true;
         } else if (state == TS_FIRST || state == TS_LIPSEQ) {
             // psi at the half step, the same point on every wavefront.  TS_FIRST (first step of an inner problem): evaluated
@@ -437,7 +438,7 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
             const double cost_half = o.psi;
             if (panoc_lip_test_fails(cx, cost_half, cost, ip, ig, nfpr) && lip_it < MAX_LIP_IT && Lip < KC(K_MAX_LIP)) {
                 lb.flush();
-                panoc_lip_update<P>(kp, vl, uv, uw, gv, gw, Lip, gamma, ig, hv, hw, rv_, rw_, d2h, nfpr, ip);
+                panoc_lip_update<P, ES_STEP>(kp, vl, uv, uw, gv, gw, Lip, gamma, ig, hv, hw, rv_, rw_, d2h, nfpr, ip);
                 ++lip_it;
                 ev = hv; ew = hw;  // want_grad stays as it is
                 continue;
@@ -452,7 +453,7 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
                 ++n_eval; ++n_eval_grad;
                 uv = hv; uw = hw;
                 cost = uniform(o.psi); gv = o.gv; gw = o.gw;
-                panoc_envelope_sums<P>(kp, vl, uv, uw, gamma, gv, gw, hv, hw, gg, d2h);
+                panoc_envelope_sums<P, ES_STEP>(kp, vl, uv, uw, gamma, gv, gw, hv, hw, gg, d2h);
                 TEAM_TRACE(-1, 1.0);
                 ++iter;
                 step_begin = true;
@@ -472,7 +473,7 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
             ++n_eval; ++n_eval_grad;
             uv = ev; uw = ew;
             cost = uniform(o.psi); gv = o.gv; gw = o.gw;
-            panoc_envelope_sums<P>(kp, vl, uv, uw, gamma, gv, gw, hv, hw, gg, d2h);
+            panoc_envelope_sums<P, ES_STEP>(kp, vl, uv, uw, gamma, gv, gw, hv, hw, gg, d2h);
             TEAM_TRACE(nls, 0.0);
             ++iter;
             step_begin = true;
