@@ -219,6 +219,20 @@ __host__ __device__ constexpr bool gram_square(int N, int mem) { return MPC_LEAN
 #ifndef MPC_VALUE_ONLY
 #define MPC_VALUE_ONLY 1
 #endif
+// The Lipschitz test of a PANOC step is `psi(u_half) > bound && lip_it < MAX_LIP_IT && L < K_MAX_LIP`, and psi(u_half) is read by
+// nothing else.  Once L stands at its cap (it never falls inside an inner problem) or the step has had its ten updates, the test is
+// CLOSED (panoc_lip_test_open): the evaluation cannot change a later bit, and it is not run.  Nothing behind the test reads what the
+// evaluation leaves: `o` is written by the next evaluation before it is read, and positions, hinge sums, stash and item partials are
+// scratch the evaluation initialises itself (the L-BFGS step writes every slot of its alias XA / COEF / P2 before it reads it).
+// n_eval still counts the evaluation the sequential algorithm specifies (as for the speculative passes of the latency kernel).  An
+// open test is the former code.  0 = every specified evaluation runs, instruction for instruction (`make variants`:
+// libmpcgpu_lipskip0.so, the bitwise yardstick and A/B partner: tests/test_gpu_lip_skip.py, profiles/lip_skip_ab.txt).
+// Dead share by the oracle's trace (tools/lip_saturation.py): 15-20 % of the Lipschitz evaluations of the benchmark family at N_hor = 20,
+// 30 % at 40, none in the passing family.  On the MI355X against the 0 build: -2.69 % VALU instructions per solve, -2.3 % kernel time on
+// the benchmark leg; +0.35 % on the passing family, which pays the comparison and has nothing to skip.
+#ifndef MPC_LIP_SKIP
+#define MPC_LIP_SKIP 1
+#endif
 // The item phase of eval_point trimmed to its arithmetic for the compiled shape N_hor = 20 (uniform lane split, one problem per
 // wavefront; lean_items() below): the lane roles from 24-bit arithmetic, one lane base per table for the cached dynamic-row trips
 // (the trips are compile-time distances from it: LPS = 3), one definition of the zeros the guarded regions start from, the doubled
@@ -2109,6 +2123,11 @@ __device__ __forceinline__ bool panoc_lip_test_fails(const Ctx& cx, double cost_
     const double rhs_lip = cost + KC(K_EPS_LIP) * fabs(cost) - ip + (KC(K_GAMMA_L) * 0.5 * ig) * nfpr * nfpr;
     return cost_half > rhs_lip;
 }
+// Is the Lipschitz test open, i.e. may its outcome still lead to an update?  Closed once L has reached its cap or the step has had
+// its MAX_LIP_IT updates: psi(u_half) then feeds a comparison nobody acts on (see MPC_LIP_SKIP).  Wave-uniform.
+__device__ __forceinline__ bool panoc_lip_test_open(const Ctx& cx, int lip_it, int max_lip_it, double Lip) {
+    return lip_it < max_lip_it && Lip < KC(K_MAX_LIP);
+}
 // L <- 2L, gamma <- gamma / 2, new half step, fpr and the sums that belong to it
 template <class P, bool ES = false>
 __device__ __forceinline__ void panoc_lip_update(const KParams& kp, bool vl, double uv, double uw, double gv, double gw, double& Lip,
@@ -2819,6 +2838,11 @@ __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& i
         PROF_MARK(10 + state);  // solver logic that led to this evaluation (by the state it was issued for)
         PROF_COUNT(16 + state);
         ++n_eval; n_eval_grad += want_grad ? 1 : 0;
+#if MPC_LIP_SKIP && !MPC_STEP_LOOP
+        // (one call site for every state: a closed Lipschitz test is specified and counted, not run)
+        const bool lip_closed = state == ST_LIP && !panoc_lip_test_open(cx, lip_it, MAX_LIP_IT, Lip);
+        if (!lip_closed)
+#endif
         eval_point<NT, SC, P, AXIS, LIN, MINW>(kp, cx, ev, ew, c, icm, ya, yb, want_grad, state == ST_OUTER, o PROF_PASS);
         bool step_begin = false;
 
@@ -2837,6 +2861,9 @@ __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& i
 #if !MPC_STEP_LOOP
         else if (state == ST_LIP) {
             const double cost_half = o.psi;
+#if MPC_LIP_SKIP
+            if (lip_closed) {} else   // (cost_half is the number of an earlier evaluation)
+#endif
             if (panoc_lip_test_fails(cx, cost_half, cost, ip, ig, nfpr) && lip_it < MAX_LIP_IT && Lip < KC(K_MAX_LIP)) {
                 lb.flush();  // invalidate the L-BFGS buffer
                 panoc_lip_update<P, ES_STEP>(kp, vl, uv, uw, gv, gw, Lip, gamma, ig, hv, hw, rv_, rw_, d2h, nfpr, ip);
@@ -2973,6 +3000,12 @@ __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& i
                     inner_done = true;
                 if (inner_done) break;
                 lip_it = 0;
+                // MPC_LIP_SKIP: the test is asked IN FRONT of the loop and behind an update, not at the loop's head -- an exit of the loop
+                // ahead of its inlined evaluation moved the register allocation of the whole step (profiles/lip_skip_ab.txt, section 1)
+#if MPC_LIP_SKIP
+                if (__builtin_expect(!panoc_lip_test_open(cx, lip_it, MAX_LIP_IT, Lip), 0)) ++n_eval;   // closed: specified, counted, not run
+                else
+#endif
                 for (;;) {   // Lipschitz test at the half step
                     PROF_MARK(10 + ST_LIP);
                     PROF_COUNT(16 + ST_LIP);
@@ -2983,6 +3016,9 @@ __device__ __forceinline__ void solve_body(const KParams& kp, const BatchPtrs& i
                         lb.flush();  // invalidate the L-BFGS buffer
                         panoc_lip_update<P, ES_STEP>(kp, vl, uv, uw, gv, gw, Lip, gamma, ig, hv, hw, rv_, rw_, d2h, nfpr, ip);
                         ++lip_it;
+#if MPC_LIP_SKIP
+                        if (!panoc_lip_test_open(cx, lip_it, MAX_LIP_IT, Lip)) { ++n_eval; break; }
+#endif
                         continue;
                     }
                     break;

@@ -417,6 +417,13 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
         PROF_MARK(19);    // (profile builds: slots 10 verdict barrier, 11 adoption, 12 L-BFGS pair + direction, 14 step residual, 15 end of a pass -> its
         PROF_COUNT(16);   //  verdict, 18 bookkeeping of a completed step, 19 direction -> next pass incl. the loop's back edge, 13 the rest; counts: 16 passes,
                           //  17 PANOC steps; wavefront 0 of every team reports)
+        // A closed Lipschitz test (MPC_LIP_SKIP) is specified and counted, not run: TS_LIPSEQ only -- the evaluation of TS_FIRST is the next
+        // iterate's, and the Lipschitz wavefront of a speculative pass runs beside the trials (skipping it does not shorten the pass).
+        // Lip and lip_it are the same on every wavefront of the team: all of them skip, or none.
+#if MPC_LIP_SKIP
+        const bool lip_closed = state == TS_LIPSEQ && !panoc_lip_test_open(cx, lip_it, MAX_LIP_IT, Lip);
+        if (!lip_closed)
+#endif
         eval_point<NT, SC, P>(kp, cx, ev, ew, c, icm, ya, yb, want_grad, state == TS_OUTER, o PROF_PASS);
 
         if (state == TS_INIT0) {
@@ -436,6 +443,9 @@ __global__ __launch_bounds__(WAVE * TW) MPC_TEAM_ATTR void solve_kernel_team(KPa
             // WITH the gradient, because once the Lipschitz test passes this very point becomes the iterate.
             ++n_eval;
             const double cost_half = o.psi;
+#if MPC_LIP_SKIP
+            if (lip_closed) {} else   // (cost_half is the number of an earlier evaluation)
+#endif
             if (panoc_lip_test_fails(cx, cost_half, cost, ip, ig, nfpr) && lip_it < MAX_LIP_IT && Lip < KC(K_MAX_LIP)) {
                 lb.flush();
                 panoc_lip_update<P, ES_STEP>(kp, vl, uv, uw, gv, gw, Lip, gamma, ig, hv, hw, rv_, rw_, d2h, nfpr, ip);
